@@ -1,7 +1,7 @@
 """Benchmark: SelectiveUNet_B training images/sec, 256x256, global batch 128 (BASELINE.json).
 
-    python bench.py [--gpus N --steps K --warmup W]                       # N = 1
-    python -m torch.distributed.run --nproc-per-node N bench.py --gpus N  # N > 1 (RCCL)
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]  # N = 1
+    python -m torch.distributed.run --nproc-per-node N bench.py --gpus N [--full]  # N > 1 (RCCL)
 
 One step = the reference's training iteration (train.py:186-209) on synthetic, HBM-resident
 data: forward of UNet_B(selective=True), BCEWithLogits aux loss + calc_selective_risk_image_b
@@ -9,11 +9,19 @@ data: forward of UNet_B(selective=True), BCEWithLogits aux loss + calc_selective
 global batch of 128 is split into contiguous per-rank chunks (DataParallel semantics), so
 `scaling` is "strong". Rank 0 prints one JSON line.
 
+A plain run does what the headline needs and no more: set-up, W warm-up steps, the K timed steps
+(`value`, `ms_per_step`), the output dump if asked for, the line. `--dump-outputs DIR` writes what
+the last timed step returned to its caller — the loss and the output, selection and auxiliary
+logits — as DIR/<name>.npy (float32; a tensor of more than DUMP_MAX_ELEMS elements as a fixed,
+seeded sample of that many; 24 MB in all for the default shape). Inputs and initial
+parameters are seeded, so two builds run with the same arguments can be compared output for output.
+Everything below is measured only with `--full` (each part has its own --no-... switch there).
+
 `value` is the fp32 configuration — the reference's arithmetic (model.py:9-15, train.py:194-209):
 fp32 tensors, statistics, losses and optimizer, with the 3x3 and ConvTranspose2d contractions on
 split-fp16 operands (each fp32 operand = fp16 high + low parts, 22 significant bits; three
 v_mfma_f32_32x32x16_f16 products per fp32 product, fp32 accumulation) — timed with no
-profiling hook installed. The same run then measures the step with every convolution on exact fp32
+profiling hook installed. With `--full` the same run then measures the step with every convolution on exact fp32
 MFMA products (`exact_f32` key, v_mfma_f32_32x32x2_f32, SELUNET_X2=0) and the bf16 speed
 configuration (`bf16` key) the same way. `step_mfma_frac` divides the step's direct-convolution
 FLOP rate by the ceiling of the arithmetic actually run: fp16 dense peak / 3 for split-fp16, the
@@ -57,6 +65,7 @@ PEAK = {"bf16": (2500.0, "TFLOP/s"), "fp32": (157.3, "TFLOP/s")}  # MI355X dense
 # ceiling of one fp32 product on split-fp16 operands: three fp16 MFMA products each
 X2_CEILING_TFLOPS = PEAK["bf16"][0] / 3
 HBM_PEAK_GBS = 8000.0
+DUMP_MAX_ELEMS = 1 << 21  # per dumped array: 8 MB of float32, 24 MB for the three logit tensors
 
 
 def parse():
@@ -81,7 +90,16 @@ def parse():
     ap.add_argument("--layer-report", action="store_true", help="print per-entry-point timing to stderr")
     ap.add_argument("--no-size512", action="store_true",
                     help="skip the BASELINE configs[4] measurement (512x512, global bs=64, `size512` key)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: exact_f32, bf16, bf16_nosel, size512, "
+                         "roofline, full_loop, input_loop, cpu_baseline (each with its --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss, logits) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if not args.full:
+        args.no_bf16 = args.no_exact = args.no_cpu_baseline = args.no_kernel_timing = True
+        args.no_full_loop = args.no_input_loop = args.no_size512 = True
+    return args
 
 
 def _i(v):
@@ -337,7 +355,23 @@ def timed(fn, steps, world, dev):
     return elapsed
 
 
-def run_config(args, dtype, world, rank, dev, xt, lt, local_batch):
+def dump_outputs(path, arrays):
+    """Write each tensor as path/<name>.npy in float32: whole up to DUMP_MAX_ELEMS elements, beyond that
+    the elements at DUMP_MAX_ELEMS flat indices drawn once from a seeded generator (the same for every
+    run of one shape): sorted(default_rng(0).choice(numel, DUMP_MAX_ELEMS, replace=False)). The indices
+    are not stored; nothing but the values is written."""
+    os.makedirs(path, exist_ok=True)
+    sample = {}  # numel -> indices
+    for name, t in arrays.items():
+        t = t.detach().to(torch.float32)
+        if t.numel() > DUMP_MAX_ELEMS:
+            if t.numel() not in sample:
+                sample[t.numel()] = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(sample[t.numel()]).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
+def run_config(args, dtype, world, rank, dev, xt, lt, local_batch, dump_dir=None):
     dt = torch.bfloat16 if dtype == "bf16" else torch.float32
     selective = bool(args.selective)
     net = S.UNet_B("RGB", selective=selective, compute_dtype=dt)
@@ -352,6 +386,7 @@ def run_config(args, dtype, world, rank, dev, xt, lt, local_batch):
     state = {}
 
     def step(x=xt, t=lt):
+        aux = None
         if selective:
             out, sel, aux = net(x)
             loss = loss_a(aux, t)
@@ -363,13 +398,16 @@ def run_config(args, dtype, world, rank, dev, xt, lt, local_batch):
         opt.zero_grad()
         loss.backward()
         opt.step()
-        state["loss"], state["out"], state["sel"] = loss, out, sel
+        state["loss"], state["out"], state["sel"], state["aux"] = loss, out, sel, aux
         return loss
 
     for _ in range(args.warmup):
         step()
     elapsed = timed(step, args.steps, world, dev)
     final_loss = float(state["loss"].item())
+    if dump_dir is not None and rank == 0:
+        # what the last timed step handed back (rank 0's chunk of the batch when N > 1)
+        dump_outputs(dump_dir, {k: state[k] for k in ("loss", "out", "sel", "aux") if state[k] is not None})
     res = {"value": round(args.batch * args.steps / elapsed, 2), "ms_per_step": round(1e3 * elapsed / args.steps, 3),
            "final_loss": round(final_loss, 5)}
 
@@ -560,7 +598,7 @@ def main():
     lt = torch.tensor(lab[lo:hi], device=dev)
     del x, lab
 
-    head = run_config(args, args.dtype, world, rank, dev, xt, lt, hi - lo)
+    head = run_config(args, args.dtype, world, rank, dev, xt, lt, hi - lo, dump_dir=args.dump_outputs)
     extra = exact = None
     if args.dtype == "fp32" and not args.no_exact and world == 1:
         # the same fp32 step on the exact-fp32-MFMA kernels (Winograd / direct), for comparison

@@ -8,7 +8,7 @@ out=$root/gpurun_out/prof_$tag
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o p -- \
-  python3 "$root/bench.py" --no-cpu-baseline --no-kernel-timing --no-full-loop --no-exact --no-bf16 "$@" \
+  python3 "$root/bench.py" --full --no-cpu-baseline --no-kernel-timing --no-full-loop --no-exact --no-bf16 "$@" \
   > "$out/run.log" 2>&1
 rc=$?
 f=$(find "$out" -name '*kernel_stats.csv' | head -1)
