@@ -19,7 +19,9 @@ import pytest
 import torch
 
 import selectivenet_for_semantic_segmentation_binary_amd as S
+from oracle import unet_b_cpu as O
 from selectivenet_for_semantic_segmentation_binary_amd.synthetic import make_batch
+from tests import _golden as G
 from tests.test_gpu_model import build
 
 pytestmark = pytest.mark.gpu
@@ -90,6 +92,63 @@ def test_replay_with_bn_shift_matches_to_rounding():
     for o in o_on[1:]:
         assert np.abs(o - o_on[0]).max() <= 1e-5 * max(1.0, np.abs(o_on[0]).max())
     assert np.allclose(l_on, l_on[0], rtol=1e-6, atol=0), l_on
+
+
+def test_replay_with_stale_bn_center_matches_oracle():
+    """The case the shifted statistics are built for: frozen weights (lr = 0, so no trajectory effect can hide
+    behind rounding) and a new batch every step, so replayed step k centres its sums on the mean of batch k - 1.
+    Every step's output against the CPU oracle's fp32 training forward of that batch on the same weights (the
+    project's forward tolerance, 1e-4 of the tensor max); after step 4 every running_mean / running_var against
+    the oracle's fp64 buffers, no further than max(3 x the oracle's own fp32 deviation from fp64, 1e-5) relative
+    to the buffer's max (the yardstick of tests/_golden.check_grads_vs_truth); and against the same four steps
+    with plans off (a zero center at every step) within the 1e-5 of test_replay_with_bn_shift_matches_to_rounding.
+    Measured on the MI355X: outputs within 2.30e-6 (replayed) and 2.34e-6 (plans off) of the oracle's fp32 run,
+    replayed within 1.66e-6 of plans off (0 at step 0), the worst running statistic at 0.018 of its bound
+    (every bound is the 1e-5 floor: the oracle's own fp32 buffers deviate from fp64 by 6e-8 .. 2.9e-7)."""
+    steps = 4
+    _, o_on, _, net_on = _run(True, lr=0.0, same_batch=False, steps=steps)
+    _, o_off, _, net_off = _run(False, lr=0.0, same_batch=False, steps=steps)
+    eng = net_on._engine()
+    assert eng.bn_shift and all(e.plan is not None for v in eng._plans.values() for e in v)
+    state = {}
+    for dt in (torch.float32, torch.float64):
+        params, buffers = O.make_state(0, "RGB", True)
+        params = {k: v.detach().to(dt) for k, v in params.items()}
+        buffers = {k: (v.to(dt) if v.is_floating_point() else v) for k, v in buffers.items()}  # carried over the steps
+        outs = []
+        with torch.no_grad():
+            for s in range(steps):
+                x, _ = make_batch(2, 64, seed=10 + s)
+                outs.append(O.forward(params, buffers, torch.tensor(x, dtype=dt), True, training=True)[0].numpy())
+        state[dt] = (outs, buffers)
+    o32, b32 = state[torch.float32]
+    o64, b64 = state[torch.float64]
+    worst_out = worst_off = worst_pair = 0.0
+    for s in range(steps):
+        e_on, e_off = G.max_rel(o_on[s], o32[s]), G.max_rel(o_off[s], o32[s])
+        pair = np.abs(o_on[s] - o_off[s]).max() / max(1.0, np.abs(o_off[s]).max())
+        print(f"step {s}: output vs oracle fp32: replayed {e_on:.2e}, eager {e_off:.2e} (vs oracle fp64: "
+              f"{G.max_rel(o_on[s], o64[s]):.2e}, {G.max_rel(o_off[s], o64[s]):.2e}); replayed vs eager {pair:.2e}")
+        worst_out, worst_off, worst_pair = max(worst_out, e_on), max(worst_off, e_off), max(worst_pair, pair)
+    worst_ratio = 0.0
+    fails = []
+    for net, tag in ((net_on, "replayed"), (net_off, "eager")):
+        for k, v in net.named_buffers():
+            if k.endswith("num_batches_tracked"):
+                assert int(v) == steps, k
+            if "running" not in k:
+                continue
+            bound = max(3.0 * G.max_rel(b32[k].numpy(), b64[k].numpy()), 1e-5)
+            dev = G.max_rel(v.cpu().numpy(), b64[k].numpy())
+            worst_ratio = max(worst_ratio, dev / bound)
+            if dev > bound:
+                fails.append(f"{tag} {k}: {dev:.2e} > {bound:.2e}")
+    print(f"worst output deviation vs oracle fp32: replayed {worst_out:.2e}, eager {worst_off:.2e}; replayed vs "
+          f"eager {worst_pair:.2e}; worst running-statistic deviation / bound {worst_ratio:.3f}")
+    assert worst_out < 1e-4 and worst_off < 1e-4
+    assert not fails, "\n".join(fails)
+    assert worst_pair <= 1e-5
+    assert not np.array_equal(o_on[0], o_on[1])  # (the batches do differ)
 
 
 def test_dropped_graph_releases_plan_and_eval_forward_replays():
