@@ -1442,12 +1442,73 @@ conv3x3_wgrad_x2_kernel(GatherArg P, GatherArg Q, int ldo, int co_tiles, int ci_
   // (pixel px of a tile is stored by chunk px % ci_chunks), so no chunk's workgroups carry all of them
   const bool dy_out = BNA && bn.dy != nullptr;
 
-  auto tile_origin = [&](int pt, int& img, int& y0, int& x0) __attribute__((always_inline)) {
-    const unsigned r2 = (unsigned)pt / (unsigned)tiles_x;
-    x0 = ((unsigned)pt - r2 * (unsigned)tiles_x) * XTW;
-    const unsigned r3 = r2 / (unsigned)tiles_y;
-    y0 = (r2 - r3 * (unsigned)tiles_y) * XTH;
-    img = (int)r3;
+  // Staging addresses. A thread's place in a tile is the same for every tile, so everything per thread is formed
+  // here, once: 32-bit byte offsets from the tile's origin (dY tile, halo) and one word of predicate bits, tb.
+  // A tile then costs a few scalar instructions (tile_geo: the 64-bit pixel index of its origin and the mask em
+  // of the image edges it touches), an access is (scalar base) + (32-bit offset), and a predicate is tb & em.
+  // tb: bits 4r..4r+3, halo round r: the slot is in halo row 0 / below the image in the last tile row / in halo
+  // column 0 / right of the image in the last tile column (ragged last tiles have hrem x wrem pixels); bit 16+r,
+  // dY round r: the pixel's row is below the image in the last tile row (POOL: bit 16, the window's); bit 20: its
+  // column is right of the image in the last tile column; bit 24+r: this workgroup stores dy of round r (POOL:
+  // of window pixel r). Out-of-image elements are read at an address inside the tile and staged as zeros (loads
+  // predicated on the bits instead: exec-masked blocks in the k-step body, 0.3 % slower, profiles/r07a_wgrad_index.txt).
+  constexpr int PPR = 512 / (BI / 4);            // dY pixels per round: PPR / XTW whole tile rows
+  const int hrem = H - (tiles_y - 1) * XTH, wrem = W - (tiles_x - 1) * XTW;
+  const int pcc = tid % (BI / 4);
+  unsigned tb = 0, p_off, g_off = 0, w_off = 0, x_off[X_ROUNDS];
+  if constexpr (POOL) {  // window tid / (BI / 4) of the tile, channels pcc * 4
+    const int wn = tid / (BI / 4), wyy = 2 * (wn / (XTW / 2)), wxx = 2 * (wn % (XTW / 2));
+    p_off = (unsigned)((wyy * W + wxx) * pa.C + pcc * 4) * 4u;
+    w_off = (unsigned)(((wyy / 2) * (W / 2) + wxx / 2) * pa.C + pcc * 4) * 4u;
+    if (wyy >= hrem) tb |= 1u << 16;
+    if (wxx >= wrem) tb |= 1u << 20;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (((wyy + (k >> 1)) * XTW + wxx + (k & 1)) % ci_chunks == cik) tb |= 1u << (24 + k);
+  } else {
+    const int px = tid / (BI / 4), py = px / XTW, pxx = px % XTW;
+    p_off = (unsigned)((py * W + pxx) * pa.C + pcc * 4) * 4u;
+    if constexpr (HEADS) g_off = (unsigned)(py * W + pxx) * 4u;
+    if (pxx >= wrem) tb |= 1u << 20;
+#pragma unroll
+    for (int r = 0; r < P_ROUNDS; ++r) {
+      if (py + r * (PPR / XTW) >= hrem) tb |= 1u << (16 + r);
+      if (BNA && (r * PPR + px) % ci_chunks == cik) tb |= 1u << (24 + r);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < X_ROUNDS; ++r) {
+    const int hp = min((r * 512 + tid) >> 4, XHP - 1), hy = hp / XHW, hx = hp % XHW;
+    x_off[r] = (unsigned)((hy * W + hx) * xa.C + (tid & 15) * 4) * 4u;  // from halo slot (0, 0): pixel (y0 - 1, x0 - 1)
+    tb |= (unsigned)((hy == 0) | (hy > hrem) << 1 | (hx == 0) << 2 | (hx > wrem) << 3) << (4 * r);
+  }
+  const unsigned p_rstride = (unsigned)((PPR / XTW) * W * pa.C) * 4u;  // bytes between a thread's dY rounds
+  const unsigned g_rstride = (unsigned)((PPR / XTW) * W) * 4u;         // HEADS: the same in a gradient plane
+  const unsigned x_safe = (unsigned)((W + 1) * xa.C) * 4u;             // halo slot (1, 1): the tile's first pixel
+  struct Geo {
+    int64_t pix;   // (img H + y0) W + x0
+    int64_t hpix;  // POOL: the same in the pooled grid
+    unsigned em;   // the tile's image edges, against tb
+  };
+  auto tile_geo = [&](int pt_) __attribute__((always_inline)) {
+    const unsigned pt = (unsigned)__builtin_amdgcn_readfirstlane(pt_);  // wave-uniform: scalar arithmetic
+    const unsigned r2 = pt / (unsigned)tiles_x, tx = pt - r2 * (unsigned)tiles_x;
+    const unsigned r3 = r2 / (unsigned)tiles_y, ty = r2 - r3 * (unsigned)tiles_y;
+    Geo g;
+    g.pix = ((int64_t)r3 * H + ty * XTH) * W + tx * XTW;
+    g.hpix = POOL ? ((int64_t)r3 * (H / 2) + ty * (XTH / 2)) * (W / 2) + tx * (XTW / 2) : 0;
+    g.em = (ty == 0 ? 0x1111u : 0u) | (ty == (unsigned)tiles_y - 1u ? 0x0f2222u : 0u) |
+           (tx == 0 ? 0x4444u : 0u) | (tx == (unsigned)tiles_x - 1u ? 0x108888u : 0u);
+    return g;
+  };
+  // in-image predicates of dY round r (POOL: of the thread's window) and of halo round r
+  auto p_in = [&](const Geo& g, int r) __attribute__((always_inline)) {
+    return (tb & g.em & ((POOL ? 1u << 16 : 1u << (16 + r)) | 1u << 20)) == 0;
+  };
+  auto x_in = [&](const Geo& g, int r) __attribute__((always_inline)) { return (tb & g.em & (0xfu << (4 * r))) == 0; };
+  // (uniform base) + (32-bit unsigned byte offset): a scalar base register pair with a VGPR offset
+  auto at = [&](const void* base, int64_t elems, unsigned off) __attribute__((always_inline)) {
+    return reinterpret_cast<const char*>(reinterpret_cast<const float*>(base) + elems) + (size_t)off;
   };
   // 4 fp32 channels -> (BN+ReLU) -> scale -> h / l fp16 quads at plane rows hp / lp
   auto put = [&](float4 v, const float* sc, const float* sh, int relu, float s, _Float16* hp, _Float16* lp)
@@ -1475,63 +1536,54 @@ conv3x3_wgrad_x2_kernel(GatherArg P, GatherArg Q, int ldo, int co_tiles, int ci_
   float4 wy[POOL ? 4 : 1], wk[POOL ? 4 : 1], wg;  // POOL: y and skip at a window's 4 pixels, the pooled gradient
   // rounds [r0, r1) of the dY tile (BNA at BI = 128 stages it in two halves: dA and y of half a tile live
   // at a time, as many registers as the plain kernel's whole dY tile)
-  auto load_p = [&](int pt, int r0, int r1) __attribute__((always_inline)) {
-    int img, y0, x0;
-    tile_origin(pt, img, y0, x0);
-    if constexpr (POOL) {  // window wi = tid / (BI / 4) of the tile, channels (tid % (BI / 4)) * 4
+  auto load_p = [&](const Geo& g, int r0, int r1) __attribute__((always_inline)) {
+    const int64_t e0 = g.pix * pa.C + i0;  // the tile's first dY element (channel i0 of its first pixel)
+    if constexpr (POOL) {  // window tid / (BI / 4) of the tile, channels (tid % (BI / 4)) * 4
       if (r0 == 0 && tid < NWIN) {
-        const int wi = tid / (BI / 4), cg = tid % (BI / 4);
-        const int yy = min(y0 + 2 * (wi / (XTW / 2)), H - 2), xx = min(x0 + 2 * (wi % (XTW / 2)), W - 2);
-        const int64_t b0 = (((int64_t)img * H + yy) * W + xx) * pa.C + i0 + cg * 4, rs = (int64_t)W * pa.C;
-        const int64_t off[4] = {b0, b0 + pa.C, b0 + rs, b0 + rs + pa.C};
+        // (a window below or right of the image reads the tile's first window instead: H, W even)
+        const bool in = p_in(g, 0);
+        const unsigned o = in ? p_off : 0u;
+        const int64_t rs = (int64_t)W * pa.C;
+        const int64_t ek[4] = {e0, e0 + pa.C, e0 + rs, e0 + rs + pa.C};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          wy[k] = *reinterpret_cast<const float4*>(bn.y + off[k]);
-          wk[k] = bn.skip ? *reinterpret_cast<const float4*>(bn.skip + off[k]) : make_float4(0, 0, 0, 0);
+          wy[k] = *reinterpret_cast<const float4*>(at(bn.y, ek[k], o));
+          wk[k] = bn.skip ? *reinterpret_cast<const float4*>(at(bn.skip, ek[k], o)) : make_float4(0, 0, 0, 0);
         }
-        wg = *reinterpret_cast<const float4*>(
-            bn.pooled + (((int64_t)img * (H / 2) + yy / 2) * (W / 2) + xx / 2) * pa.C + i0 + cg * 4);
+        wg = *reinterpret_cast<const float4*>(at(bn.pooled, g.hpix * pa.C + i0, in ? w_off : 0u));
       }
       return;
     }
 #pragma unroll
     for (int r = 0; r < P_ROUNDS; ++r) {
       if (r < r0 || r >= r1) continue;
-      const int idx = r * 512 + tid;
-      const int px = idx / (BI / 4), cc = idx % (BI / 4);
-      const int y = min(y0 + px / XTW, H - 1), x = min(x0 + px % XTW, W - 1);
-      const int64_t pix = ((int64_t)img * H + y) * W + x;
-      const int64_t off = pix * pa.C + i0 + cc * 4;
+      // (a pixel below or right of the image reads the tile's first pixel instead)
+      const bool in = p_in(g, r);
+      const unsigned o = in ? p_off + r * p_rstride : 0u;
       if constexpr (HEADS) {
-        rg[r][0] = bn.g0[pix];
-        rg[r][1] = bn.nh > 1 ? bn.g1[pix] : 0.0f;
-        rg[r][2] = bn.nh > 1 ? bn.g2[pix] : 0.0f;
+        const unsigned go = in ? g_off + r * g_rstride : 0u;
+        rg[r][0] = *reinterpret_cast<const float*>(at(bn.g0, g.pix, go));
+        rg[r][1] = bn.nh > 1 ? *reinterpret_cast<const float*>(at(bn.g1, g.pix, go)) : 0.0f;
+        rg[r][2] = bn.nh > 1 ? *reinterpret_cast<const float*>(at(bn.g2, g.pix, go)) : 0.0f;
       } else {
-        rp[r] = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(pa.data) + off);
+        rp[r] = *reinterpret_cast<const float4*>(at(pa.data, e0, o));
       }
-      if constexpr (BNA) ry[r] = *reinterpret_cast<const float4*>(bn.y + off);
+      if constexpr (BNA) ry[r] = *reinterpret_cast<const float4*>(at(bn.y, e0, o));
     }
   };
-  auto load_x = [&](int pt) __attribute__((always_inline)) {
-    int img, y0, x0;
-    tile_origin(pt, img, y0, x0);
+  auto load_x = [&](const Geo& g) __attribute__((always_inline)) {
+    const int64_t e0 = (g.pix - W - 1) * xa.C + xc;  // halo slot (0, 0); only in-image slots are dereferenced
 #pragma unroll
-    for (int r = 0; r < X_ROUNDS; ++r) {
-      const int idx = r * 512 + tid;
-      const int hp = min(idx >> 4, XHP - 1), cc = idx & 15;
-      const int y = min(max(y0 - 1 + hp / XHW, 0), H - 1), x = min(max(x0 - 1 + hp % XHW, 0), W - 1);
-      rx[r] = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(xa.data) +
-                                               (((int64_t)img * H + y) * W + x) * xa.C + xc + cc * 4);
-    }
+    for (int r = 0; r < X_ROUNDS; ++r)
+      rx[r] = *reinterpret_cast<const float4*>(at(xa.data, e0, x_in(g, r) ? x_off[r] : x_safe));
   };
-  auto store_p = [&](int pt, int buf, int r0, int r1) __attribute__((always_inline)) {
-    int img, y0, x0;
-    tile_origin(pt, img, y0, x0);
+  auto store_p = [&](const Geo& tl, int buf, int r0, int r1) __attribute__((always_inline)) {
+    const int64_t e0 = tl.pix * pa.C + i0;
     if constexpr (POOL) {
       if (r0 == 0 && tid < NWIN) {
         const int wi = tid / (BI / 4), cg = tid % (BI / 4);
         const int wyy = 2 * (wi / (XTW / 2)), wxx = 2 * (wi % (XTW / 2));
-        const bool in = y0 + wyy < H && x0 + wxx < W;  // (H, W even: a window is wholly in or out)
+        const bool in = p_in(tl, 0);  // (H, W even: a window is wholly in or out)
         const f32x4 csc = *reinterpret_cast<const f32x4*>(Ks + cg * 4);
         const f32x4 csh = *reinterpret_cast<const f32x4*>(Ks + BI + cg * 4);
         const f32x4 ck0 = *reinterpret_cast<const f32x4*>(Ks + 2 * BI + cg * 4);
@@ -1564,9 +1616,9 @@ conv3x3_wgrad_x2_kernel(GatherArg P, GatherArg Q, int ldo, int co_tiles, int ci_
           }
           const int py = wyy + (k >> 1), pxx = wxx + (k & 1), px = py * XTW + pxx;
           const float4 dv = in ? make_float4(o[0], o[1], o[2], o[3]) : make_float4(0, 0, 0, 0);
-          if (dy_out && in && px % ci_chunks == cik) {
-            const int64_t off = (((int64_t)img * H + y0 + py) * W + x0 + pxx) * pa.C + i0 + cg * 4;
-            *reinterpret_cast<float4*>(bn.dy + off) = dv;
+          if (dy_out && in && (tb & (1u << (24 + k)))) {
+            const int64_t ek = e0 + ((k >> 1) * (int64_t)W + (k & 1)) * pa.C;
+            *reinterpret_cast<float4*>(const_cast<char*>(at(bn.dy, ek, p_off))) = dv;
             dam = fmaxf(dam, fmaxf(fmaxf(fabsf(dv.x), fabsf(dv.y)), fmaxf(fabsf(dv.z), fabsf(dv.w))));
           }
           put(dv, nullptr, nullptr, 0, sp, &Ps[buf][0][px][cg * 4], &Ps[buf][1][px][cg * 4]);
@@ -1579,7 +1631,7 @@ conv3x3_wgrad_x2_kernel(GatherArg P, GatherArg Q, int ldo, int co_tiles, int ci_
       if (r < r0 || r >= r1) continue;
       const int idx = r * 512 + tid;
       const int px = idx / (BI / 4), cc = idx % (BI / 4);
-      const bool in = y0 + px / XTW < H && x0 + px % XTW < W;
+      const bool in = p_in(tl, r);
       if constexpr (BNA) {
         // dy of 4 channels (bn_bwd_apply_kernel's arithmetic)
         float g[4] = {rp[r].x, rp[r].y, rp[r].z, rp[r].w};
@@ -1602,9 +1654,8 @@ conv3x3_wgrad_x2_kernel(GatherArg P, GatherArg Q, int ldo, int co_tiles, int ci_
         for (int e = 0; e < 4; ++e)
           o[e] = (yv[e] * csc[e] + csh[e] > 0.0f ? ck0[e] * g[e] : 0.0f) - cb[e] - ca[e] * yv[e];
         const float4 d = in ? make_float4(o[0], o[1], o[2], o[3]) : make_float4(0, 0, 0, 0);
-        if (dy_out && in && px % ci_chunks == cik) {
-          const int64_t off = (((int64_t)img * H + y0 + px / XTW) * W + x0 + px % XTW) * pa.C + i0 + cc * 4;
-          *reinterpret_cast<float4*>(bn.dy + off) = d;
+        if (dy_out && in && (tb & (1u << (24 + r)))) {
+          *reinterpret_cast<float4*>(const_cast<char*>(at(bn.dy, e0 + r * (int64_t)(p_rstride / 4), p_off))) = d;
           dam = fmaxf(dam, fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fmaxf(fabsf(d.z), fabsf(d.w))));
         }
         put(d, nullptr, nullptr, 0, sp, &Ps[buf][0][px][cc * 4], &Ps[buf][1][px][cc * 4]);
@@ -1614,16 +1665,13 @@ conv3x3_wgrad_x2_kernel(GatherArg P, GatherArg Q, int ldo, int co_tiles, int ci_
       }
     }
   };
-  auto store_x = [&](int pt, int buf) __attribute__((always_inline)) {
-    int img, y0, x0;
-    tile_origin(pt, img, y0, x0);
+  auto store_x = [&](const Geo& g, int buf) __attribute__((always_inline)) {
 #pragma unroll
     for (int r = 0; r < X_ROUNDS; ++r) {
       const int idx = r * 512 + tid;
       if (idx < XHP * 16) {
         const int hp = idx >> 4, cc = idx & 15;
-        const int y = y0 - 1 + hp / XHW, x = x0 - 1 + hp % XHW;
-        const bool in = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
+        const bool in = x_in(g, r);
         put(in ? rx[r] : make_float4(0, 0, 0, 0), xa.scale && in ? Ks + KX + cc * 4 : nullptr,
             Ks + KX + 64 + cc * 4, xa.relu, sx, &Xs[buf][0][hp][cc * 4], &Xs[buf][1][hp][cc * 4]);
       }
@@ -1635,11 +1683,12 @@ conv3x3_wgrad_x2_kernel(GatherArg P, GatherArg Q, int ldo, int co_tiles, int ci_
   for (int t = 0; t < NTAP; ++t) acc[t] = f32x16{};
 
   if (pt_first < pt_stop) {
-    load_p(pt_first, 0, P_ROUNDS);
-    load_x(pt_first);
+    const Geo g0 = tile_geo(pt_first);
+    load_p(g0, 0, P_ROUNDS);
+    load_x(g0);
     __syncthreads();  // coefficients visible
-    store_p(pt_first, 0, 0, P_ROUNDS);
-    store_x(pt_first, 0);
+    store_p(g0, 0, 0, P_ROUNDS);
+    store_x(g0, 0);
     __syncthreads();
   }
   typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
@@ -1661,13 +1710,14 @@ conv3x3_wgrad_x2_kernel(GatherArg P, GatherArg Q, int ldo, int co_tiles, int ci_
       // quarters, stored after k-steps 0 and 2)
       constexpr bool QSPLIT = BNA && BI == 128;
       constexpr int PH = QSPLIT ? P_ROUNDS / 2 : P_ROUNDS;
-      load_p(more ? ptn : pt, 0, PH);
+      const Geo gn = tile_geo(more ? ptn : pt);  // the tile staged during this one's MFMAs
+      load_p(gn, 0, PH);
       __builtin_amdgcn_sched_barrier(0);  // keep the next tile's loads ahead of this tile's MFMAs
 #pragma unroll
       for (int ks = 0; ks < XPIX / 16; ++ks) {  // two tile rows (16 pixels) per k-step
         if (QSPLIT && ks == 1) {
-          if (more) store_p(ptn, buf ^ 1, 0, PH);
-          load_p(more ? ptn : pt, PH, P_ROUNDS);
+          if (more) store_p(gn, buf ^ 1, 0, PH);
+          load_p(gn, PH, P_ROUNDS);
           __builtin_amdgcn_sched_barrier(0);
         }
         // (QSPLIT: the second dY half is stored at k-step 3, two k-steps after its loads, and the halo's loads get
@@ -1676,12 +1726,12 @@ conv3x3_wgrad_x2_kernel(GatherArg P, GatherArg Q, int ldo, int co_tiles, int ci_
         // the halo loaded at k-step 1 and the dY tile stored at k-step 3, three k-steps of cover each: 3-4 %,
         // profiles/r05q_wgrad64_schedule_ab.txt)
         if (BI == 64 && ks == 1) {
-          load_x(more ? ptn : pt);
+          load_x(gn);
           __builtin_amdgcn_sched_barrier(0);
         }
         if (ks == (QSPLIT || BI == 64 ? 3 : 2)) {
-          if (more) store_p(ptn, buf ^ 1, QSPLIT ? PH : 0, P_ROUNDS);
-          if (BI != 64) load_x(more ? ptn : pt);
+          if (more) store_p(gn, buf ^ 1, QSPLIT ? PH : 0, P_ROUNDS);
+          if (BI != 64) load_x(gn);
           __builtin_amdgcn_sched_barrier(0);
         }
         if constexpr (TQ) {
@@ -1697,7 +1747,9 @@ conv3x3_wgrad_x2_kernel(GatherArg P, GatherArg Q, int ldo, int co_tiles, int ci_
           f16x8 h, l;
         };
         auto read_tap = [&](int t) __attribute__((always_inline)) {
-          const int tap = min(tap0 + t, 8);
+          // (the loop's tap count fixes its first tap: a constant, so the halo rows are immediates)
+          constexpr int TAP0 = TG == 2 && NTP == 4 ? 5 : 0;
+          const int tap = min(TAP0 + t, 8);
           const int dy = tap / 3, dx = tap - (tap / 3) * 3;
           const int xrow = (2 * ks + half + dy) * XHW + dx + q4;
           Frag f;
@@ -1726,7 +1778,7 @@ conv3x3_wgrad_x2_kernel(GatherArg P, GatherArg Q, int ldo, int co_tiles, int ci_
       if constexpr (TQ) {
         if (tid == 0) tq_slot[buf] = (int)min(claimed, (unsigned)pt_stop);  // read after the barrier
       }
-      if (more) store_x(ptn, buf ^ 1);
+      if (more) store_x(gn, buf ^ 1);
       __syncthreads();
       if constexpr (TQ) pt_tq = tq_slot[buf];
       pt = ptn;
