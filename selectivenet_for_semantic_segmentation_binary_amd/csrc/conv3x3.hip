@@ -437,6 +437,112 @@ conv3x3_halo_persist_kernel(GatherArg g, const T* __restrict__ B, int N, int k_p
     return reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(sa.data) +
                                           (((int64_t)img * g.h + ys) * g.w + xs) * sa.C + c + cc * E);
   };
+  // X2: staging addresses formed once (as conv3x3_wgrad_x2_kernel). A halo round is three whole halo rows
+  // (54 pixels x 8 slices = 432 threads; threads 432.. repeat the round's pixels 0..9: the same bytes to
+  // the same LDS slot), so a thread's place (row xry of the three, column, slice xcc) is the same in every
+  // round and the rounds differ by a uniform stride. Per thread: the pixel offset xpix from the round's
+  // first halo slot, the LDS byte offset xlds of its slot in round 0 (odd rounds: ^ 16, the row parity of
+  // halo_off's swizzle), the weight byte offset xb_off, and predicate bits xtb: bit r: the slot of round r
+  // is in halo row 0, 6 + r: below the image in the last tile row, 12 + r: in halo column 0, 18 + r: right
+  // of the image in the last tile column (ragged last tiles have hrem x wrem pixels). Per tile, in scalar
+  // registers (tile_geo): the 64-bit pixel index of the origin and the mask em of the image edges it
+  // touches. A load is (scalar base) + (32-bit offset); an out-of-image slot reads the tile's own first
+  // pixel and is staged as zeros.
+  constexpr int XRPIX = 3 * HWT;  // halo pixels per round
+  static_assert(!X2 || (A_ROUNDS * 3 == HHT && XRPIX * 8 <= HTHREADS), "three halo rows per round");
+  const int xq = tid >> 3, xcc = tid & 7;
+  const int xhp = xq < XRPIX ? xq : xq - XRPIX;
+  const int xry = (xhp >= HWT) + (xhp >= 2 * HWT), xhx = xhp - xry * HWT;
+  const unsigned xpix = (unsigned)(xry * g.w + xhx);
+  const unsigned xb_off = (unsigned)(xq * k_pad * 4 + xcc * 16);
+  const unsigned xb_rstride = (unsigned)(64 * k_pad * 4);  // bytes between a thread's weight rounds
+  auto x_lds = [](int t) __attribute__((always_inline)) {
+    const int q = t >> 3, cc = t & 7, hp = q < XRPIX ? q : q - XRPIX;
+    const int ry = (hp >= HWT) + (hp >= 2 * HWT);
+    return (unsigned)(hp * AROWB + (((cc >> 1) ^ (ry & 1)) << 4) + (cc & 1) * 8);
+  };
+  const unsigned xlds = x_lds(tid);
+  unsigned xtb = 0;
+  if constexpr (X2) {
+    const int hrem = g.h - (tiles_y - 1) * TH, wrem = g.w - (tiles_x - 1) * TW;
+#pragma unroll
+    for (int r = 0; r < A_ROUNDS; ++r) {
+      const int hy = 3 * r + xry;
+      xtb |= (unsigned)((hy == 0) | (hy > hrem) << 6 | (xhx == 0) << 12 | (xhx > wrem) << 18) << r;
+    }
+  }
+  struct Geo {
+    int img, y0, x0;
+    int64_t pix;  // (img h + y0) w + x0
+    unsigned em;  // the tile's image edges, against xtb
+  };
+  auto tile_geo = [&](int pt_) __attribute__((always_inline)) {
+    const unsigned pt = (unsigned)__builtin_amdgcn_readfirstlane(pt_);  // wave-uniform: scalar arithmetic
+    const unsigned r = pt / (unsigned)tiles_x, tx = pt - r * (unsigned)tiles_x;
+    const unsigned r2 = r / (unsigned)tiles_y, ty = r - r2 * (unsigned)tiles_y;
+    Geo q;
+    q.img = (int)r2;
+    q.y0 = (int)ty * TH;
+    q.x0 = (int)tx * TW;
+    q.pix = ((int64_t)r2 * g.h + ty * TH) * g.w + tx * TW;
+    q.em = (ty == 0 ? 0x3fu : 0u) | (ty == (unsigned)tiles_y - 1u ? 0x3fu << 6 : 0u) |
+           (tx == 0 ? 0x3fu << 12 : 0u) | (tx == (unsigned)tiles_x - 1u ? 0x3fu << 18 : 0u);
+    return q;
+  };
+  // one chunk's halo staging: scalar element index of halo slot (0, 0) (pixel (y0 - 1, x0 - 1): only
+  // in-image slots are dereferenced), the thread's byte offset in round 0, the uniform round stride,
+  // the offset of the tile's first pixel, and the out-of-image bits of the thread's six slots
+  struct XStage {
+    int64_t e0;
+    unsigned off, rstride, safe, out;
+  };
+  auto x_stage = [&](const Geo& q, const SrcArg& sa, int c) __attribute__((always_inline)) {
+    XStage s;
+    s.e0 = (q.pix - g.w - 1) * sa.C + c;
+    s.off = __umul24(xpix, (unsigned)sa.C * 4u) + (unsigned)xcc * 16u;  // (24-bit factors: launch_x2)
+    s.rstride = (unsigned)(3 * g.w * sa.C) * 4u;
+    s.safe = (unsigned)((g.w + 1) * sa.C) * 4u;
+    s.out = xtb & q.em;
+    return s;
+  };
+  auto x_out = [](const XStage& s, int r) __attribute__((always_inline)) { return (s.out & (0x41041u << r)) != 0; };
+  // (uniform base) + (32-bit unsigned byte offset): a scalar base register pair with a VGPR offset
+  auto at = [](const void* base, int64_t elems, unsigned off) __attribute__((always_inline)) {
+    return reinterpret_cast<const uint4*>(
+        reinterpret_cast<const char*>(reinterpret_cast<const float*>(base) + elems) + (size_t)off);
+  };
+  auto x_load = [&](const XStage& s, const SrcArg& sa, int r) __attribute__((always_inline)) {
+    unsigned rs = (unsigned)r * s.rstride;
+    asm volatile("" : "+s"(rs));  // (kept a scalar 32-bit addend: known ranges widen the sum to a 64-bit multiply-add)
+    return *at(sa.data, s.e0, x_out(s, r) ? s.safe : s.off + rs);
+  };
+  // 4 fp32 values -> scale 2^e -> fp16 split: high parts in .x/.y, low parts in .z/.w
+  auto x_split4 = [&](uint4 v) __attribute__((always_inline)) {
+#ifdef SELUNET_ABL_RAW_HALO  // timing-only ablation (results wrong): the raw bits, no transform, no split
+    return v;
+#else
+    float f[4];
+    __builtin_memcpy(f, &v, 16);
+    f16x4 h, l;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      _Float16 a, b;
+      x2_split(f[e] * xs, a, b);
+      h[e] = a;
+      l[e] = b;
+    }
+    uint4 o;
+    __builtin_memcpy(&o.x, &h, 8);
+    __builtin_memcpy(&o.z, &l, 8);
+    return o;
+#endif
+  };
+  // a split slice of round r to halo buffer hb (lds: the thread's xlds)
+  auto x_put = [&](int hb, int r, unsigned lds, uint4 o) __attribute__((always_inline)) {
+    unsigned char* p = As + hb * HPIX * AROWB + r * (XRPIX * AROWB) + (lds ^ ((unsigned)(r & 1) << 4));
+    *reinterpret_cast<uint2*>(p) = make_uint2(o.x, o.y);
+    *reinterpret_cast<uint2*>(p + 64) = make_uint2(o.z, o.w);
+  };
   struct BRegs {
     uint4 v[B_ROUNDS];
   };
@@ -444,6 +550,16 @@ conv3x3_halo_persist_kernel(GatherArg g, const T* __restrict__ B, int N, int k_p
     const int chunk = st / 9, tap = st - chunk * 9;
     const int k0 = tap * g.Ctot + chunk * CK;
     BRegs rb;
+    if constexpr (X2) {
+      // scalar base of the step; the largest packed weight is below 2^31 B (launch_x2). (The offset is made
+      // opaque here: hoisted out of the loop it is widened to a 64-bit pair and every load pays a 64-bit add.)
+      const int64_t e0 = (int64_t)n0 * k_pad + k0;
+      unsigned o = xb_off;
+      asm volatile("" : "+v"(o));
+#pragma unroll
+      for (int r = 0; r < B_ROUNDS; ++r) rb.v[r] = *at(B, e0, o + (unsigned)r * xb_rstride);
+      return rb;
+    }
 #pragma unroll
     for (int r = 0; r < B_ROUNDS; ++r) {
       const int idx = r * HTHREADS + tid;
@@ -559,20 +675,34 @@ conv3x3_halo_persist_kernel(GatherArg g, const T* __restrict__ B, int N, int k_p
   };
 
   // ---------------------------------------------------------------- prologue: tile 0 chunk 0, B(0), B(1)
+  Geo gc{}, gn{};  // X2: this tile and the next one
+  if constexpr (X2) gc = gn = tile_geo(TQ ? pt_cur : prow);
   if (!TQ || pt_cur < ptiles) {
-    int img, y0, x0;
-    tile_xy(TQ ? pt_cur : prow, img, y0, x0);
     int c0;
     const SrcArg sa = chunk_src(0, c0);
     uint4 v0[A_ROUNDS];
+    if constexpr (X2) {
+      const XStage s0 = x_stage(gc, sa, c0);
 #pragma unroll
-    for (int r = 0; r < A_ROUNDS; ++r) {
-      int hp, cc;
-      a_slot(r, hp, cc);
-      v0[r] = *a_ptr(sa, c0, img, y0, x0, hp, cc);
+      for (int r = 0; r < A_ROUNDS; ++r) v0[r] = x_load(s0, sa, r);
+#pragma unroll
+      for (int r = 0; r < A_ROUNDS; ++r) {
+        uint4 o = make_uint4(0, 0, 0, 0);
+        if (!x_out(s0, r)) o = sa.scale ? transform16<T>(v0[r], sa.scale, sa.shift, c0 + xcc * E, sa.relu) : v0[r];
+        x_put(0, r, xlds, x_split4(o));
+      }
+    } else {
+      int img, y0, x0;
+      tile_xy(TQ ? pt_cur : prow, img, y0, x0);
+#pragma unroll
+      for (int r = 0; r < A_ROUNDS; ++r) {
+        int hp, cc;
+        a_slot(r, hp, cc);
+        v0[r] = *a_ptr(sa, c0, img, y0, x0, hp, cc);
+      }
+#pragma unroll
+      for (int r = 0; r < A_ROUNDS; ++r) halo_put_global(v0[r], r, sa, c0, y0, x0, 0);
     }
-#pragma unroll
-    for (int r = 0; r < A_ROUNDS; ++r) halo_put_global(v0[r], r, sa, c0, y0, x0, 0);
   }
   BRegs rb_next = b_load(0);
   b_store(rb_next, 0);
@@ -592,20 +722,32 @@ conv3x3_halo_persist_kernel(GatherArg g, const T* __restrict__ B, int N, int k_p
   unsigned claimed = 0;  // TQ: the ticket tid 0 claims during a tile
   for (int i = 0; TQ ? pt_cur < ptiles : i < ntl; ++i) {
     int img, y0, x0;
-    tile_xy(TQ ? pt_cur : prow + i * gp, img, y0, x0);
+    if constexpr (X2) {
+      img = gc.img, y0 = gc.y0, x0 = gc.x0;
+      if constexpr (!TQ) gn = i + 1 < ntl ? tile_geo(prow + (i + 1) * gp) : gc;
+    } else {
+      tile_xy(TQ ? pt_cur : prow + i * gp, img, y0, x0);
+    }
     BRegs rb_hold;
     for (int c = 0; c < nchunks; ++c, ++J) {
       if constexpr (TQ) {
-        if (c == 1) pt_next = tq_slot;  // the ticket claimed at chunk 0 (nchunks >= 2)
+        if (c == 1) {
+          pt_next = tq_slot;  // the ticket claimed at chunk 0 (nchunks >= 2)
+          gn = pt_next < ptiles ? tile_geo(pt_next) : gc;
+        }
       }
       const bool last_c = c + 1 == nchunks;
       const bool has_next = !last_c || (TQ ? pt_next < ptiles : i + 1 < ntl);
       const bool defer = last_c && has_next;  // next job is the next tile: LDS writes after the epilogue
       int nimg = img, ny0 = y0, nx0 = x0;
-      if (defer) tile_xy(TQ ? pt_next : prow + (i + 1) * gp, nimg, ny0, nx0);
+      if constexpr (!X2) {
+        if (defer) tile_xy(TQ ? pt_next : prow + (i + 1) * gp, nimg, ny0, nx0);
+      }
       const int nc = !has_next ? c : (last_c ? 0 : c + 1);
       int cs;
       const SrcArg sn = chunk_src(nc, cs);
+      XStage sx{};
+      if constexpr (X2) sx = x_stage(defer ? gn : gc, sn, cs);
       float* ssc = Ss + ((J + 1) & 1) * CK;
       float* ssh = Ss + 2 * CK + ((J + 1) & 1) * CK;
       float coef = 0.0f;
@@ -617,9 +759,13 @@ conv3x3_halo_persist_kernel(GatherArg g, const T* __restrict__ B, int N, int k_p
 #pragma unroll
         for (int r = 0; r < A_ROUNDS; ++r) {
           if (halo_load_tap(r) == t) {
-            int hp, cc;
-            a_slot(r, hp, cc);
-            ra[r] = *a_ptr(sn, cs, nimg, ny0, nx0, hp, cc);
+            if constexpr (X2) {
+              ra[r] = x_load(sx, sn, r);
+            } else {
+              int hp, cc;
+              a_slot(r, hp, cc);
+              ra[r] = *a_ptr(sn, cs, nimg, ny0, nx0, hp, cc);
+            }
           }
         }
         if constexpr (TQ) {
@@ -635,6 +781,30 @@ conv3x3_halo_persist_kernel(GatherArg g, const T* __restrict__ B, int N, int k_p
 #pragma unroll
         for (int r = 0; r < A_ROUNDS; ++r) {
           if (halo_write_tap(r) != t) continue;
+          if constexpr (X2) {
+            // no branch on the slot: every thread has one, and an out-of-image one is a select to zero
+            uint4 v = ra[r];
+#ifndef SELUNET_ABL_RAW_HALO
+            if (sn.scale) {
+              float e[4];
+              __builtin_memcpy(e, &v, 16);
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                float f = e[j] * ssc[xcc * 4 + j] + ssh[xcc * 4 + j];
+                if (sn.relu) f = fmaxf(f, 0.0f);
+                e[j] = f;
+              }
+              __builtin_memcpy(&v, e, 16);
+            }
+            if (x_out(sx, r)) v = make_uint4(0, 0, 0, 0);
+#endif
+            // defer: the next tile's first job is transformed and split here, under this job's MFMAs, and
+            // written to LDS after the epilogue (which uses the whole LDS) with no global reads
+            const uint4 o = x_split4(v);
+            if (!defer) x_put((J + 1) & 1, r, xlds, o);
+            else ra[r] = o;
+            continue;
+          }
           int hp, cc;
           if (a_slot(r, hp, cc)) {
             uint4 v = make_uint4(0, 0, 0, 0);
@@ -740,13 +910,18 @@ conv3x3_halo_persist_kernel(GatherArg g, const T* __restrict__ B, int N, int k_p
       asm volatile("" : "+v"(tid2));
 #pragma unroll
       for (int r = 0; r < A_ROUNDS; ++r) {
-        const int hidx = r * HTHREADS + tid2;
-        if (hidx < HPIX * 8) halo_store_prepped(J & 1, hidx >> 3, hidx & 7, ra[r]);  // (transformed in the last job)
+        if constexpr (X2) {
+          x_put(J & 1, r, x_lds(tid2), ra[r]);  // (transformed and split in the last job)
+        } else {
+          const int hidx = r * HTHREADS + tid2;
+          if (hidx < HPIX * 8) halo_store_prepped(J & 1, hidx >> 3, hidx & 7, ra[r]);  // (transformed in the last job)
+        }
       }
       b_store(rb_hold, S & 1);
       __syncthreads();
     }
     if constexpr (TQ) pt_cur = pt_next;
+    gc = gn;
   }
   if constexpr (TQ) {
     if (ts.amax) block_amax(ts.amax, amx, tile);
@@ -2608,6 +2783,12 @@ static int launch_x2(const GatherArg& g, const float* w, int N, const EpiArg& ep
   const int n_tiles = N / BN;
   const int gp = persist_rows(g, N);  // workgroups per column tile (static: = the statistics slab rows)
   const int k_pad = 9 * g.Ctot;
+  // the kernel's staging offsets are 32-bit byte offsets from a scalar base (the packed weights with their
+  // row scales; a halo tile's last slot of either source) and its pixel-offset product has 24-bit factors
+  const int cmax = std::max(g.src[0].C, g.nsrc > 1 ? g.src[1].C : 0);
+  if (((int64_t)N * k_pad + N) * 4 >= (int64_t)1 << 31 || (int64_t)(HHT * g.w + HWT) * cmax * 4 >= (int64_t)1 << 31 ||
+      (int64_t)3 * g.w + HWT >= 1 << 24 || (int64_t)cmax * 4 >= 1 << 24)
+    return fail(SELUNET_EINVAL, "conv3x3_x2: operand too large for 32-bit staging offsets");
   // 16x16x32 MFMAs at BN = 64 (1-4 % faster per layer); at BN = 128 they cost 20-25 % (the extra
   // fragment registers spill: 180 B of scratch per lane against 44) — DESIGN.md §3
   if (x2_tile_queue()) {

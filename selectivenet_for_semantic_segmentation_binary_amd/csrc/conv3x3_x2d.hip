@@ -64,13 +64,84 @@ conv3x3_x2d_kernel(GatherArg g, const float* __restrict__ B, int k_pad, EpiArg e
 #pragma unroll
   for (int b = 0; b < 4; ++b) cfac[b] = wcs[b * 16 + l16] * inv;
 
-  auto tile_xy = [&](int i, int& img, int& y0, int& x0) __attribute__((always_inline)) {
-    const unsigned pt = (unsigned)(prow + i * gp);
-    const unsigned r = pt / (unsigned)tiles_x;
-    x0 = (int)(pt - r * (unsigned)tiles_x) * XD_TW;
-    const unsigned r2 = r / (unsigned)tiles_y;
-    y0 = (int)(r - r2 * (unsigned)tiles_y) * XD_TH;
-    img = (int)r2;
+  // Staging addresses, formed once (as conv3x3_halo_persist_kernel<float, BN, X2>). The 11 halo rounds of 32
+  // pixels are: rounds 0..8 rows 2r + (q >> 4), columns q & 15 (q = tid >> 3), a uniform stride apart; round 9
+  // columns 16 + (q & 1) of rows q >> 1 (0..15); round 10 the same columns of rows 16, 17 (threads 0..31). So a
+  // thread has two pixel offsets (pa, pb) from halo slot (0, 0), two LDS byte offsets (a_store) and one word of
+  // predicate bits tb: bit r: the slot of round r is in halo row 0, 11 + r: below the image in the last tile
+  // row, 22 / 23: rounds 0..8 in halo column 0 / right of the image in the last tile column, 24: rounds 9, 10
+  // right of it, 25: no slot in round 10. Per tile, in scalar registers: the 64-bit pixel index of the origin
+  // and the mask em of the image edges the tile touches. A load is (scalar base) + (32-bit offset); an
+  // out-of-image slot reads the tile's own first pixel and is staged as zeros.
+  const int sq = tid >> 3, scc = tid & 7;
+  const int say = sq >> 4, sax = sq & 15, sby = sq >> 1, sbx = 16 + (sq & 1);
+  auto lds_of = [](int hy, int hx, int cc) __attribute__((always_inline)) {
+    return (unsigned)((hy * XD_HW + hx) * XD_AROWB + (cc & 1) * 8 + (((cc >> 1) ^ (hy & 1)) << 4));
+  };
+  unsigned tb = 0;
+  {
+    const int hrem = g.h - (tiles_y - 1) * XD_TH, wrem = g.w - (tiles_x - 1) * XD_TW;
+#pragma unroll
+    for (int r = 0; r < XD_A_ROUNDS; ++r) {
+      const int hy = r < 9 ? 2 * r + say : (r == 9 ? sby : 16 + sby);
+      tb |= (unsigned)((hy == 0) | (hy > hrem) << 11) << r;
+    }
+    tb |= (unsigned)(sax == 0) << 22 | (unsigned)(sax > wrem) << 23 | (unsigned)(sbx > wrem) << 24 |
+          (unsigned)(tid >= 32) << 25;
+  }
+  struct Geo {
+    int img, y0, x0;
+    int64_t pix;  // (img h + y0) w + x0
+    unsigned em;  // the tile's image edges, against tb
+  };
+  auto tile_geo = [&](int i) __attribute__((always_inline)) {
+    const unsigned pt = (unsigned)__builtin_amdgcn_readfirstlane(prow + i * gp);  // wave-uniform: scalar arithmetic
+    const unsigned r = pt / (unsigned)tiles_x, tx = pt - r * (unsigned)tiles_x;
+    const unsigned r2 = r / (unsigned)tiles_y, ty = r - r2 * (unsigned)tiles_y;
+    Geo q;
+    q.img = (int)r2;
+    q.y0 = (int)ty * XD_TH;
+    q.x0 = (int)tx * XD_TW;
+    // (the divisions are expanded in vector registers: back to scalar ones, or every use is vector arithmetic)
+    const int64_t pix = ((int64_t)r2 * g.h + ty * XD_TH) * g.w + tx * XD_TW;
+    q.pix = (int64_t)(((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(pix >> 32)) << 32) |
+                      (unsigned)__builtin_amdgcn_readfirstlane((int)pix));
+    q.em = (unsigned)__builtin_amdgcn_readfirstlane(
+        (int)((ty == 0 ? 0x7ffu : 0u) | (ty == (unsigned)tiles_y - 1u ? 0x7ffu << 11 : 0u) | (tx == 0 ? 1u << 22 : 0u) |
+              (tx == (unsigned)tiles_x - 1u ? 3u << 23 : 0u) | 1u << 25));
+    return q;
+  };
+  // one job's halo staging: scalar element index of halo slot (0, 0) (only in-image slots are dereferenced),
+  // the thread's byte offsets, the uniform strides, the tile's first pixel, the out-of-image bits of its 11 slots
+  struct XStage {
+    int64_t e0;
+    unsigned oa, ob, stride_a, stride_b, safe, out;
+  };
+  auto x_stage = [&](const Geo& q, const SrcArg& sa, int c) __attribute__((always_inline)) {
+    XStage s;
+    s.e0 = (q.pix - g.w - 1) * sa.C + c;
+    // (the thread's pixel offsets pa, pb from halo slot (0, 0), re-formed from tid per job: kept, they are spilled)
+    int tq = tid;
+    asm volatile("" : "+v"(tq));
+    const unsigned tp = (unsigned)tq >> 3, c16 = ((unsigned)tq & 7u) * 16u;
+    const unsigned pa = __umul24(tp >> 4, (unsigned)g.w) + (tp & 15u);
+    const unsigned pb = __umul24(tp >> 1, (unsigned)g.w) + 16u + (tp & 1u);
+    s.oa = __umul24(pa, (unsigned)sa.C * 4u) + c16;  // (24-bit factors: conv3x3_x2d_launch)
+    s.ob = __umul24(pb, (unsigned)sa.C * 4u) + c16;
+    s.stride_a = (unsigned)(2 * g.w * sa.C) * 4u;
+    s.stride_b = (unsigned)(16 * g.w * sa.C) * 4u;
+    s.safe = (unsigned)((g.w + 1) * sa.C) * 4u;
+    s.out = tb & q.em;
+    return s;
+  };
+  auto x_out = [](const XStage& s, int r) __attribute__((always_inline)) {
+    const unsigned m = 1u << r | 1u << (11 + r) | (r < 9 ? 3u << 22 : 1u << 24) | (r == 10 ? 1u << 25 : 0u);
+    return (s.out & m) != 0;
+  };
+  // (uniform base) + (32-bit unsigned byte offset): a scalar base register pair with a VGPR offset
+  auto at = [](const void* base, int64_t elems, unsigned off) __attribute__((always_inline)) {
+    return reinterpret_cast<const uint4*>(
+        reinterpret_cast<const char*>(reinterpret_cast<const float*>(base) + elems) + (size_t)off);
   };
   auto chunk_src = [&](int chunk, int& c) -> SrcArg {
     c = chunk * XD_CK;
@@ -86,26 +157,25 @@ conv3x3_x2d_kernel(GatherArg g, const float* __restrict__ B, int k_pad, EpiArg e
   auto b_load = [&](int st) __attribute__((always_inline)) {  // st: step within a tile (chunk * 9 + tap)
     const int chunk = st / 9, tap = st - chunk * 9;
     const int k0 = tap * g.Ctot + chunk * XD_CK;
+    // scalar base of the step + the thread's fixed offset (row q, slice cc; 32 rows per round); the packed weights
+    // are below 2^31 B (conv3x3_x2d_launch). (The offset is made opaque here: hoisted out of the
+    // loop it is widened to a 64-bit pair and every load pays a 64-bit add.)
     int tq = tid;
     asm volatile("" : "+v"(tq));
+    unsigned o = __umul24((unsigned)tq >> 3, (unsigned)k_pad * 4u) + ((unsigned)tq & 7u) * 16u;
+    asm volatile("" : "+v"(o));
     BRegs rb;
 #pragma unroll
-    for (int r = 0; r < XD_B_ROUNDS; ++r) {
-      const int idx = r * XD_THREADS + tq;
-      const int row = idx >> 3, cc = idx & 7;
-      rb.v[r] = *reinterpret_cast<const uint4*>(B + (int64_t)row * k_pad + k0 + cc * 4);
-    }
+    for (int r = 0; r < XD_B_ROUNDS; ++r) rb.v[r] = *at(B, k0, o + (unsigned)r * (32u * (unsigned)k_pad * 4u));
     return rb;
   };
   auto b_store = [&](const BRegs& rb, int buf) __attribute__((always_inline)) {
     int tq = tid;
     asm volatile("" : "+v"(tq));
+    const unsigned o = __umul24((unsigned)tq >> 3, (unsigned)XD_WROWB) + ((unsigned)tq & 7u) * 16u;  // row tq >> 3
 #pragma unroll
-    for (int r = 0; r < XD_B_ROUNDS; ++r) {
-      const int idx = r * XD_THREADS + tq;
-      const int row = idx >> 3, cc = idx & 7;
-      *reinterpret_cast<uint4*>(Bs + (buf * XD_BN + row) * XD_WROWB + cc * 16) = rb.v[r];
-    }
+    for (int r = 0; r < XD_B_ROUNDS; ++r)  // (32 rows per round)
+      *reinterpret_cast<uint4*>(Bs + (buf * XD_BN + r * 32) * XD_WROWB + o) = rb.v[r];
   };
 
   // ---------------------------------------------------------------- halo (raw fp32 -> split fp16)
@@ -113,35 +183,22 @@ conv3x3_x2d_kernel(GatherArg g, const float* __restrict__ B, int k_pad, EpiArg e
   struct ARegs {
     uint4 v[XD_A_ROUNDS];
   };
-  auto a_load = [&](ARegs& ra, int job, int r0, int r1) __attribute__((always_inline)) {
-    int img, y0, x0, c;
-    tile_xy(job / nchunks, img, y0, x0);
-    const SrcArg sa = chunk_src(job % nchunks, c);
-    int tq = tid;
-    asm volatile("" : "+v"(tq));
+  auto a_load = [&](ARegs& ra, const XStage& s, const SrcArg& sa, int r0, int r1) __attribute__((always_inline)) {
 #pragma unroll
     for (int r = 0; r < XD_A_ROUNDS; ++r) {
       if (r < r0 || r >= r1) continue;
-      const int hp = min((r * XD_THREADS + tq) >> 3, XD_HPIX - 1);
-      const int hy = hp / XD_HW, hx = hp - hy * XD_HW;
-      const int ys = min(max(y0 - 1 + hy, 0), g.h - 1), xq = min(max(x0 - 1 + hx, 0), g.w - 1);
-      ra.v[r] = *reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(sa.data) +
-                                                (((int64_t)img * g.h + ys) * g.w + xq) * sa.C + c + (tq & 7) * 4);
+      unsigned rs = r < 9 ? (unsigned)r * s.stride_a : (r == 9 ? 0u : s.stride_b);
+      asm volatile("" : "+s"(rs));  // (kept a scalar 32-bit addend)
+      ra.v[r] = *at(sa.data, s.e0, x_out(s, r) ? s.safe : (r < 9 ? s.oa : s.ob) + rs);
     }
   };
   // in registers: BN+ReLU of the chunk's source (sc/sh for this thread's 4 channels, or none), zero
   // outside the image, scale 2^e, fp16 split: each 16-B slice becomes 8 B of high + 8 B of low parts
-  auto a_split = [&](ARegs& ra, int job, bool tr, const float* sc, const float* sh, int relu)
+  auto a_split = [&](ARegs& ra, const XStage& s, bool tr, const float* sc, const float* sh, int relu)
       __attribute__((always_inline)) {
-    int img, y0, x0;
-    tile_xy(job / nchunks, img, y0, x0);
-    int tq = tid;
-    asm volatile("" : "+v"(tq));
 #pragma unroll
     for (int r = 0; r < XD_A_ROUNDS; ++r) {
-      const int hp = min((r * XD_THREADS + tq) >> 3, XD_HPIX - 1);
-      const int hy = hp / XD_HW, hx = hp - hy * XD_HW;
-      const bool in = (unsigned)(y0 - 1 + hy) < (unsigned)g.h && (unsigned)(x0 - 1 + hx) < (unsigned)g.w;
+      const bool in = !x_out(s, r);
       f32x4 v;
       __builtin_memcpy(&v, &ra.v[r], 16);
       f16x4 h, l;
@@ -165,29 +222,21 @@ conv3x3_x2d_kernel(GatherArg g, const float* __restrict__ B, int k_pad, EpiArg e
     }
   };
   // the split slices to the halo tile: high parts of channel group cc at 16-B unit (cc >> 1), low parts at
-  // 4 + (cc >> 1), both XOR the halo line's parity (conflict-free fragment reads, as halo_off)
+  // 4 + (cc >> 1), both XOR the halo line's parity (conflict-free fragment reads, as halo_off); the rounds of
+  // a thread keep their line parity (2 r and 16 rows apart)
   auto a_store = [&](const ARegs& ra) __attribute__((always_inline)) {
     int tq = tid;
     asm volatile("" : "+v"(tq));
-    const int cc = tq & 7;
+    const int q = tq >> 3, cc = tq & 7;
+    const unsigned sa_ = lds_of(q >> 4, q & 15, cc), sb_ = lds_of(q >> 1, 16 + (q & 1), cc);
 #pragma unroll
     for (int r = 0; r < XD_A_ROUNDS; ++r) {
-      const int hidx = r * XD_THREADS + tq;
-      if (hidx >= XD_HPIX * 8) continue;
-      const int hp = hidx >> 3;
-      const int par = (hp / XD_HW) & 1;
-      unsigned char* base = As + hp * XD_AROWB + (cc & 1) * 8;
-      *reinterpret_cast<uint2*>(base + (((cc >> 1) ^ par) << 4)) = make_uint2(ra.v[r].x, ra.v[r].y);
-      *reinterpret_cast<uint2*>(base + (((4 + (cc >> 1)) ^ par) << 4)) = make_uint2(ra.v[r].z, ra.v[r].w);
+      if (r == 10 && tq >= 32) continue;
+      unsigned char* p = As + (r < 9 ? sa_ + r * 2 * XD_HW * XD_AROWB : sb_ + (r == 10 ? 16 * XD_HW * XD_AROWB : 0));
+      *reinterpret_cast<uint2*>(p) = make_uint2(ra.v[r].x, ra.v[r].y);
+      *reinterpret_cast<uint2*>(p + 64) = make_uint2(ra.v[r].z, ra.v[r].w);
     }
   };
-  auto coef_load = [&](int job) __attribute__((always_inline)) -> float {
-    int c;
-    const SrcArg sa = chunk_src(job % nchunks, c);
-    if (tid >= 2 * XD_CK || !sa.scale) return 0.0f;
-    return tid < XD_CK ? sa.scale[c + tid] : sa.shift[c + tid - XD_CK];
-  };
-
   // ---------------------------------------------------------------- MFMA tap (16x16x32)
   f32x4 acc[4][4];
   auto mma_tap = [&](int bbuf, int t) __attribute__((always_inline)) {
@@ -217,10 +266,12 @@ conv3x3_x2d_kernel(GatherArg g, const float* __restrict__ B, int k_pad, EpiArg e
 
   // ---------------------------------------------------------------- prologue: job 0
   ARegs ra;
+  Geo gc = tile_geo(0), gn = gc;  // this tile and the next one
   if (njobs > 0) {
-    a_load(ra, 0, 0, XD_A_ROUNDS);
     int c0;
     const SrcArg sa = chunk_src(0, c0);
+    const XStage s0 = x_stage(gc, sa, c0);
+    a_load(ra, s0, sa, 0, XD_A_ROUNDS);
     float sc[4] = {1, 1, 1, 1}, sh[4] = {0, 0, 0, 0};
     if (sa.scale) {
 #pragma unroll
@@ -229,7 +280,7 @@ conv3x3_x2d_kernel(GatherArg g, const float* __restrict__ B, int k_pad, EpiArg e
         sh[e] = sa.shift[c0 + (tid & 7) * 4 + e];
       }
     }
-    a_split(ra, 0, sa.scale != nullptr, sc, sh, sa.relu);
+    a_split(ra, s0, sa.scale != nullptr, sc, sh, sa.relu);
     a_store(ra);
   }
   b_store(b_load(0), 0);
@@ -243,8 +294,8 @@ conv3x3_x2d_kernel(GatherArg g, const float* __restrict__ B, int k_pad, EpiArg e
   float creg = 0.0f;
   int J = 0, S = 0;
   for (int i = 0; i < ntl; ++i) {
-    int img, y0, x0;
-    tile_xy(i, img, y0, x0);
+    const int img = gc.img, y0 = gc.y0, x0 = gc.x0;
+    gn = i + 1 < ntl ? tile_geo(i + 1) : gc;
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -254,16 +305,17 @@ conv3x3_x2d_kernel(GatherArg g, const float* __restrict__ B, int k_pad, EpiArg e
       const bool has_next = J + 1 < njobs;
       const bool last_c = c + 1 == nchunks;
       int cn;
-      const SrcArg sn = chunk_src((J + 1) % nchunks, cn);
+      const SrcArg sn = chunk_src(last_c ? 0 : c + 1, cn);  // job J + 1: the next chunk, or the next tile's first
+      const XStage sx = x_stage(last_c ? gn : gc, sn, cn);
       float* ssn = Ss + ((J + 1) & 1) * 2 * XD_CK;
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
         const int st2 = c * 9 + t + 2;
         const BRegs rb_far = b_load(st2 < csteps ? st2 : st2 - csteps);  // (the next tile's steps wrap)
         if (has_next) {
-          if (t == 0) creg = coef_load(J + 1);
+          if (t == 0 && tid < 2 * XD_CK && sn.scale) creg = tid < XD_CK ? sn.scale[cn + tid] : sn.shift[cn + tid - XD_CK];
           // the next job's halo, two 16-B slices per tap from tap 0 (held in registers: one halo buffer)
-          if (t < (XD_A_ROUNDS + 1) / 2) a_load(ra, J + 1, 2 * t, 2 * t + 2);
+          if (t < (XD_A_ROUNDS + 1) / 2) a_load(ra, sx, sn, 2 * t, 2 * t + 2);
         }
         mma_tap(S & 1, t);
         if (t == 1 && has_next && tid < 2 * XD_CK) ssn[tid] = creg;
@@ -276,7 +328,7 @@ conv3x3_x2d_kernel(GatherArg g, const float* __restrict__ B, int k_pad, EpiArg e
               sh[e] = ssn[XD_CK + (tid & 7) * 4 + e];
             }
           }
-          a_split(ra, J + 1, sn.scale != nullptr, sc, sh, sn.relu);
+          a_split(ra, sx, sn.scale != nullptr, sc, sh, sn.relu);
         }
         if (last_c && has_next && t == 8) rb_hold = rb_next;  // B(S + 1): stored after the epilogue
         else b_store(rb_next, (S + 1) & 1);
@@ -316,6 +368,7 @@ conv3x3_x2d_kernel(GatherArg g, const float* __restrict__ B, int k_pad, EpiArg e
       b_store(rb_hold, S & 1);
       __syncthreads();
     }
+    gc = gn;
   }
   tile_stats_flush<N, XD_THREADS>(tile, tid, ts, s1, s2, s3, amx);
 }
@@ -343,6 +396,12 @@ int conv3x3_x2d_launch(const GatherArg& g, const float* w, const EpiArg& ep, con
   const int ptiles = (int)((int64_t)g.n * tiles_x * tiles_y);
   const int gp = (int)conv3x3_x2d_rows(g);
   const int k_pad = 9 * g.Ctot;
+  // the kernel's staging offsets are 32-bit byte offsets from a scalar base; its pixel-offset product has 24-bit factors
+  const int cmax = std::max(g.src[0].C, g.nsrc > 1 ? g.src[1].C : 0);
+  if (((int64_t)XD_BN * k_pad + XD_BN) * 4 >= (int64_t)1 << 31 ||
+      (int64_t)((XD_TH + 2) * g.w + XD_HW) * cmax * 4 >= (int64_t)1 << 31 || (int64_t)16 * g.w + XD_HW >= 1 << 24 ||
+      (int64_t)cmax * 4 >= 1 << 24 || (int64_t)k_pad * 4 >= 1 << 24)
+    return fail(SELUNET_EINVAL, "conv3x3_x2d: operand too large for 32-bit staging offsets");
   hipLaunchKernelGGL(conv3x3_x2d_kernel, dim3((unsigned)gp), dim3(XD_THREADS), 0, st, g, w, k_pad, ep, tiles_x, tiles_y,
                      ptiles, gp, w + (int64_t)XD_BN * k_pad, amax0, amax1);
   return check_launch("conv3x3_x2d");
