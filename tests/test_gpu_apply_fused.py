@@ -9,26 +9,60 @@ import pytest
 import torch
 
 from selectivenet_for_semantic_segmentation_binary_amd import _lib as K
-from tests.test_gpu_kernels import gen
+from tests.test_gpu_kernels import bn_state, check_signed_inputs, gen, signed_gamma
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
-def coefs(c, seed):
+def coefs(c, seed, signed=False):
+    """signed: scale, shift, mean, invstd and coef[0] = k0 of one bn_state (signed gamma), so the ReLU mask and
+    k0 carry the same sign."""
+    if signed:
+        st = bn_state(c, seed, True)
+        coef = gen(3, c, seed=seed + 4) * 0.5
+        coef[0] = st["k0"]
+        return tuple(st[k].to(DEV) for k in ("scale", "shift", "mean", "invstd")) + (coef.to(DEV).contiguous(),)
     sc, sh = (gen(c, seed=seed).abs() + 0.5).to(DEV), (gen(c, seed=seed + 1) * 0.3).to(DEV)
     mean, invstd = (gen(c, seed=seed + 2) * 0.1).to(DEV), (gen(c, seed=seed + 3).abs() + 0.5).to(DEV)
     coef = (gen(3, c, seed=seed + 4) * 0.5).to(DEV).contiguous()
     return sc, sh, mean, invstd, coef
 
 
+def check_dy_fp64(dy, amax, da, y, bn, dt):
+    """dy (and its range word) of a BN-backward apply against fp64: dy = [y*scale+shift > 0] k0 dA - k1 - k2 xhat,
+    xhat = (y - mean)*invstd, from the mask's definition alone. Bound: 1e-6 of max |dy| in fp32 (five fp32
+    operations on terms no larger than a few max |dy|; 2^-24 each), plus the bf16 unit roundoff (8 significant
+    bits: 2^-8 of the value, so of max |dy|) for a bf16 dy. Elements whose fp64 y*scale+shift lies within 1e-6
+    of the ReLU threshold (relative to |y*scale| + |shift|) take either branch in fp32: left out, at most 1e-4 of
+    all elements. The word covers max |dy|."""
+    sc, sh, mean, invstd, coef = (t.double().cpu() for t in bn)
+    y64, da64 = y.double().cpu(), da.double().cpu()
+    v = y64 * sc + sh
+    near = v.abs() <= 1e-6 * ((y64 * sc).abs() + sh.abs())
+    assert float(near.double().mean()) <= 1e-4
+    ref = (v > 0).double() * coef[0] * da64 - coef[1] - coef[2] * (y64 - mean) * invstd
+    err = ((dy.double().cpu() - ref).abs() * (~near)).max() / ref.abs().max()
+    tol = 1e-6 + (2.0 ** -8 if dt == torch.bfloat16 else 0.0)
+    print(f"apply dy against fp64: {float(err):.2e} (bound {tol:.1e})")
+    assert float(err) < tol
+    assert amax >= float((ref.abs() * (~near)).max()) * (1 - tol) > 0
+
+
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("nh", [1, 3])
 def test_apply_heads_equals_unfused(dt, nh):
+    apply_heads_case(dt, nh)
+
+
+def apply_heads_case(dt, nh, signed=False):
+    """Returns the operands and the fused results (for the signed cases' fp64 references)."""
     m = 3 * 4096 + 77  # ragged tail
     code = K.dtype_code(dt)
     y = gen(m, 64, seed=1).to(dt).to(DEV)
-    sc, sh, mean, invstd, coef = coefs(64, 10)
+    sc, sh, mean, invstd, coef = coefs(64, 10, signed)
+    if signed:
+        check_signed_inputs(sc, torch.relu(y.float() * sc + sh))
     w = (gen(3, 64, seed=2) * 0.2).to(DEV).contiguous()
     g = [(gen(m, seed=3 + i) * 1e-3).to(DEV) for i in range(3)]
     gp = [K.ptr(g[i]) if i < nh else None for i in range(3)]
@@ -55,16 +89,23 @@ def test_apply_heads_equals_unfused(dt, nh):
     assert torch.equal(s0, s1) and torch.equal(b0, b1)
     assert torch.equal(d0, d1)
     assert a0 == a1 and (dt != torch.float32 or a0 == d0.abs().max().item())  # (the word is max|dy| before rounding)
+    return dict(y=y, bn=(sc, sh, mean, invstd, coef), w=w, g=g[:nh], slab=s1, bslab=b1, dy=d1, amax=a1)
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("c,skip", [(64, True), (128, True), (256, False)])
 def test_apply_pool_equals_unfused(dt, c, skip):
+    apply_pool_case(dt, c, skip)
+
+
+def apply_pool_case(dt, c, skip, signed=False):
     n, h, w = 2, 18, 36
     code = K.dtype_code(dt)
     m = n * h * w
     y = ((gen(m, c, seed=21) * 2).round() / 2).to(dt).to(DEV)  # coarse values: ties inside the windows
-    sc, sh, mean, invstd, coef = coefs(c, 30)
+    sc, sh, mean, invstd, coef = coefs(c, 30, signed)
+    if signed:
+        check_signed_inputs(sc, torch.relu(y.float() * sc + sh))
     dp = (gen(m // 4, c, seed=22) * 1e-2).to(dt).to(DEV)
     ds = (gen(m, c, seed=23) * 1e-2).to(dt).to(DEV) if skip else None
     rows = K.query("selunet_maxpool2_bwd_slab_rows", n, h, w, c)
@@ -89,17 +130,24 @@ def test_apply_pool_equals_unfused(dt, c, skip):
     assert torch.equal(b0, b1)
     assert torch.equal(d0, d1)
     assert a0 == a1 and (dt != torch.float32 or a0 == d0.abs().max().item())  # (the word is max|dy| before rounding)
+    return dict(y=y, bn=(sc, sh, mean, invstd, coef), dp=dp, ds=ds, shape=(n, h, w, c), bslab=b1, dy=d1, amax=a1)
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 def test_apply_heads_planes_equals_unfused(dt):
     """The CE UNet's N-output heads (selunet_heads_bwd_planes / selunet_bn_bwd_apply_heads_planes): 2 images,
     outputs of 2 + 2 + 2 channels as NCHW planes."""
+    apply_heads_planes_case(dt)
+
+
+def apply_heads_planes_case(dt, signed=False):
     n, hw, nk = 2, 48 * 40, 6
     m = n * hw
     code = K.dtype_code(dt)
     y = gen(m, 64, seed=81).to(dt).to(DEV)
-    sc, sh, mean, invstd, coef = coefs(64, 90)
+    sc, sh, mean, invstd, coef = coefs(64, 90, signed)
+    if signed:
+        check_signed_inputs(sc, torch.relu(y.float() * sc + sh))
     w = (gen(8, 64, seed=82) * 0.2).to(DEV).contiguous()
     g = (gen(3, n, 2, hw, seed=83) * 1e-3).to(DEV).contiguous()  # three [N, 2, H*W] gradient tensors
     hp = K.HeadPlanes()
@@ -136,6 +184,9 @@ def test_apply_heads_planes_equals_unfused(dt):
     assert torch.equal(s0, s1) and torch.equal(b0, b1)
     assert torch.equal(d0, d1)
     assert a0 == a1
+    # dA [m][64] of plane k = (tensor k // 2, channel k % 2): sum_k g_k[m] w_k[c]
+    gk = g.reshape(3, n, 2, hw).permute(0, 2, 1, 3).reshape(nk, m)
+    return dict(y=y, bn=(sc, sh, mean, invstd, coef), w=w[:nk], g=list(gk), slab=s1, bslab=b1, dy=d1, amax=a1)
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
@@ -144,11 +195,17 @@ def test_apply_heads_planes_equals_unfused(dt):
 def test_apply_forms_equal(dt, c, form):
     """The apply kernel's alternative forms (SELUNET_OPT_APPLY_U8: 8 channels x 8 pixels, 4 contiguous
     channels x 8 / 16 pixels) against the default form, bit for bit, ragged pixel count."""
+    apply_forms_case(dt, c, form)
+
+
+def apply_forms_case(dt, c, form, signed=False):
     m = 4096 * 3 + 5
     code = K.dtype_code(dt)
     y = gen(m, c, seed=41).to(dt).to(DEV)
     dz = (gen(m, c, seed=42) * 1e-2).to(dt).to(DEV)
-    sc, sh, mean, invstd, coef = coefs(c, 50)
+    sc, sh, mean, invstd, coef = coefs(c, 50, signed)
+    if signed:
+        check_signed_inputs(sc, torch.relu(y.float() * sc + sh))
     res = []
     for f in (0, form):
         prev = K.set_option("APPLY_U8", f)
@@ -160,6 +217,7 @@ def test_apply_forms_equal(dt, c, form):
         K.set_option("APPLY_U8", prev)
         res.append((dy.float().cpu(), am.item()))
     assert torch.equal(res[0][0], res[1][0]) and res[0][1] == res[1][1]
+    return dict(y=y, bn=(sc, sh, mean, invstd, coef), da=dz, dy=res[1][0], amax=res[1][1])
 
 
 def test_sums_only_needs_the_sums():
@@ -171,7 +229,7 @@ def test_sums_only_needs_the_sums():
                K.stream_ptr())
 
 
-def _bn_state(m, c, seed):
+def _bn_state(m, c, seed, signed=False):
     """y with its real batch statistics (the Samuelson bound of selunet_bn_bwd_stats_finalize_bound holds
     for those only), the forward's folded scale / shift, and a dA."""
     g = torch.Generator().manual_seed(seed)
@@ -181,6 +239,8 @@ def _bn_state(m, c, seed):
     invstd = 1.0 / torch.sqrt(var + 1e-5)
     gamma = torch.randn(c, generator=g, dtype=torch.float64) * 0.5 + 1.0
     beta = torch.randn(c, generator=g, dtype=torch.float64) * 0.2
+    if signed:  # (after the draws above: y and dA are the unsigned case's)
+        gamma, beta = signed_gamma(c, seed).double(), beta * 2.5
     sc, sh = gamma * invstd, beta - mean * gamma * invstd
     da = torch.randn(m, c, generator=g, dtype=torch.float64) * 1e-3
     f = lambda t: t.float().to(DEV).contiguous()  # noqa: E731
@@ -191,8 +251,20 @@ def _bn_state(m, c, seed):
 def test_bn_bwd_finalize_bound_covers_dy(c):
     """selunet_bn_bwd_stats_finalize_bound: the same coefficients and parameter gradients as
     selunet_bn_bwd_stats_finalize, and a range word >= max |dy| of the apply they feed."""
+    bn_bwd_finalize_bound_case(c)
+
+
+@pytest.mark.parametrize("c", [64, 256])
+def test_bn_bwd_finalize_bound_covers_dy_signed(c):
+    """Signed gamma (k0 = gamma*invstd of either sign, exact zeros): the bound is a formula in |k0|, |k1|, |k2|."""
+    bn_bwd_finalize_bound_case(c, signed=True)
+
+
+def bn_bwd_finalize_bound_case(c, signed=False):
     m = 20000
-    y, mean, invstd, gamma, sc, sh, da = _bn_state(m, c, 5)
+    y, mean, invstd, gamma, sc, sh, da = _bn_state(m, c, 5, signed)
+    if signed:
+        check_signed_inputs(sc, torch.relu(y * sc + sh))
     mask = (y * sc + sh > 0).float()
     xh = (y - mean) * invstd
     slab = torch.stack([(da * mask).sum(0), (da * mask * xh).sum(0), xh.sum(0)]).reshape(1, 3, c).contiguous()
@@ -220,6 +292,10 @@ def test_bn_bwd_finalize_bound_covers_dy(c):
     torch.cuda.synchronize()
     assert 0.0 < am.item() <= w1
     print(f"bound / max|dy| = {w1 / am.item():.1f}")
+    # the bound is the |.| formula: max_c 1.25 (|k0| amax_da + |k1| + |k2| sqrt(count)), to fp32 rounding
+    k = c1.double().abs()
+    want = float((1.25 * (k[0] * float(amax_da) + k[1] + k[2] * m ** 0.5)).max())
+    assert abs(w1 - want) <= 1e-5 * want
 
 
 @pytest.mark.parametrize("co,ci", [(64, 64), (64, 128), (128, 128), (256, 64)])
@@ -228,15 +304,30 @@ def test_wgrad_x2_bn_equals_apply_then_wgrad(co, ci):
     selunet_bn_bwd_apply_amax + selunet_conv3x3_wgrad_x2: dy and max |dy| identical (same arithmetic),
     the weight gradient within split-fp16 rounding of it and of the fp64 weight gradient, although it
     stages dy with a looser range word (a bound 37x the exact max)."""
+    wgrad_x2_bn_case(co, ci)
+
+
+@pytest.mark.parametrize("slack", [2.0 ** 10, 2.0 ** 12])
+def test_wgrad_x2_bn_loose_words(slack):
+    """Every input range word (amax_p: the |dy| bound, amax_q0) multiplied by `slack`; dy_amax stays exact."""
+    wgrad_x2_bn_case(64, 64, slack=slack)
+
+
+def wgrad_x2_bn_case(co, ci, signed=False, slack=1.0):
     n, h, w = 2, 20, 36  # ragged 8x8 tiles in y
     m = n * h * w
-    y, mean, invstd, _, sc, sh, da = _bn_state(m, co, 7)
+    y, mean, invstd, gamma, sc, sh, da = _bn_state(m, co, 7, signed)
     coef = (gen(3, co, seed=70) * 0.5).to(DEV).contiguous()
-    coef[0] = coef[0].abs() + 0.5
+    coef[0] = gamma * invstd if signed else coef[0].abs() + 0.5  # (signed: the mask's and k0's sign are gamma's)
     x = gen(m, ci, seed=71).to(DEV)
     xsc, xsh = (gen(ci, seed=72).abs() + 0.5).to(DEV), (gen(ci, seed=73) * 0.2).to(DEV)
+    if signed:
+        xsc, xsh = signed_gamma(ci, 72).to(DEV), (gen(ci, seed=73) * 0.5).to(DEV)
+        check_signed_inputs(sc, torch.relu(y * sc + sh))
+        check_signed_inputs(xsc, torch.relu(x * xsc + xsh))
     xw = (torch.relu(x * xsc + xsh)).abs().max().reshape(1).contiguous()
-    gq = K.gather(n, h, w, 9, K.source(x, ci, xsc, xsh, relu=True, amax=xw))
+    xw_in = (xw * slack).contiguous()  # the word the kernels are given
+    gq = K.gather(n, h, w, 9, K.source(x, ci, xsc, xsh, relu=True, amax=xw_in))
     # unfused pair
     dy0 = torch.empty(m, co, device=DEV)
     am0 = torch.zeros(1, device=DEV)
@@ -247,11 +338,15 @@ def test_wgrad_x2_bn_equals_apply_then_wgrad(co, ci):
     assert wsb > 0
     ws = torch.empty(wsb // 4, device=DEV)
     dw0 = torch.empty(co, ci, 3, 3, device=DEV)
-    K.call("selunet_conv3x3_wgrad_x2", gp0, gq, K.ptr(ws), wsb, K.ptr(dw0), K.ptr(am0), K.ptr(xw), None, K.stream_ptr())
+    am0_in = (am0 * slack).contiguous()
+    K.call("selunet_conv3x3_wgrad_x2", gp0, gq, K.ptr(ws), wsb, K.ptr(dw0), K.ptr(am0_in), K.ptr(xw_in), None,
+           K.stream_ptr())
     torch.cuda.synchronize()
+    if signed:  # dy against the fp64 formula (independent of the mask's / k0's sign convention)
+        check_dy_fp64(dy0, am0.item(), da, y, (sc, sh, mean, invstd, coef), torch.float32)
     # fused (static walk, then SELUNET_OPT_TILE_QUEUE bit 1: tiles from ticket counters — dy and max |dy| are the
     # same element-wise arithmetic, the weight gradient the same sum in another order)
-    bound = (am0 * 37.0).contiguous()
+    bound = (am0 * 37.0 * slack).contiguous()
     gp1 = K.gather(n, h, w, 1, K.source(da, co))
     bnb = K.BnBwdStats(K.ptr(y), K.ptr(sc), K.ptr(sh), K.ptr(mean), K.ptr(invstd), None)
     fused = []
@@ -262,7 +357,7 @@ def test_wgrad_x2_bn_equals_apply_then_wgrad(co, ci):
             dy1 = torch.full((m, co), float("nan"), device=DEV)
             am1 = torch.zeros(1, device=DEV)
             dw1 = torch.empty(co, ci, 3, 3, device=DEV)
-            K.call("selunet_conv3x3_wgrad_x2_bn", gp1, gq, K.ptr(ws), wsb, K.ptr(dw1), K.ptr(bound), K.ptr(xw), None,
+            K.call("selunet_conv3x3_wgrad_x2_bn", gp1, gq, K.ptr(ws), wsb, K.ptr(dw1), K.ptr(bound), K.ptr(xw_in), None,
                    bnb, K.ptr(coef), K.ptr(dy1), K.ptr(am1), K.stream_ptr())
             torch.cuda.synchronize()
             assert torch.equal(dy1.cpu(), dy0.cpu()), tq
@@ -320,14 +415,17 @@ def test_sums_only_producers_record_max_da(form):
     assert wd == dz.abs().max().item() > 0
 
 
-def _src_case(form, seed=100):
+def _src_case(form, seed=100, signed=False):
     """A 64-channel layer whose dA comes from a pool (with / without skip) or the heads: the BN state,
     the dA source for selunet_conv3x3_wgrad_x2_bn_src, and a call of the standalone apply it replaces."""
     n, h, w, c = 2, 20, 36, 64  # ragged 8x8 tiles in y
     m = n * h * w
     y = ((gen(m, c, seed=seed) * 2).round() / 2).to(DEV)  # coarse: ties inside the pool windows
-    sc, sh, mean, invstd, coef = coefs(c, seed + 1)
-    coef[0] = coef[0].abs() + 0.5
+    sc, sh, mean, invstd, coef = coefs(c, seed + 1, signed)
+    if signed:  # (coef[0] = k0 = gamma*invstd of the same bn_state)
+        check_signed_inputs(sc, torch.relu(y * sc + sh))
+    else:
+        coef[0] = coef[0].abs() + 0.5
     keep = []
     if form.startswith("pool"):
         dp = (gen(m // 4, c, seed=seed + 2) * 1e-2).to(DEV)
@@ -357,10 +455,18 @@ def test_wgrad_x2_bn_src_equals_apply_then_wgrad(form):
     """selunet_conv3x3_wgrad_x2_bn_src with a pool / heads dA source (encoder_layer_1_2, decoder_layer_1_1)
     against selunet_bn_bwd_apply_pool / _heads + selunet_conv3x3_wgrad_x2: dy and max |dy| identical, the
     weight gradient within split-fp16 rounding of it and of the fp64 weight gradient."""
-    (n, h, w, c), (y, sc, sh, mean, invstd, coef), src, apply, _keep = _src_case(form)
+    wgrad_x2_bn_src_case(form)
+
+
+def wgrad_x2_bn_src_case(form, signed=False):
+    """Returns dy of the standalone apply with its operands (for the signed cases' fp64 reference)."""
+    (n, h, w, c), (y, sc, sh, mean, invstd, coef), src, apply, _keep = _src_case(form, signed=signed)
     m, ci = n * h * w, 64
     x = gen(m, ci, seed=171).to(DEV)
     xsc, xsh = (gen(ci, seed=172).abs() + 0.5).to(DEV), (gen(ci, seed=173) * 0.2).to(DEV)
+    if signed:
+        xsc, xsh = signed_gamma(ci, 172).to(DEV), (gen(ci, seed=173) * 0.5).to(DEV)
+        check_signed_inputs(xsc, torch.relu(x * xsc + xsh))
     xw = (torch.relu(x * xsc + xsh)).abs().max().reshape(1).contiguous()
     gq = K.gather(n, h, w, 9, K.source(x, ci, xsc, xsh, relu=True, amax=xw))
     dy0 = torch.empty(m, c, device=DEV)
@@ -391,6 +497,7 @@ def test_wgrad_x2_bn_src_equals_apply_then_wgrad(form):
     print(f"wgrad rel err unfused {e0:.2e} fused {e1:.2e}")
     assert e1 < 2e-6 and e0 < 2e-6
     assert rel(dw1.cpu(), dw0.cpu().double()) < 2e-6
+    return dict(y=y, bn=(sc, sh, mean, invstd, coef), shape=(n, h, w, c), keep=_keep, dy=dy0, amax=am0.item())
 
 
 def test_wgrad_x2_bn_src_argument_checks():

@@ -12,7 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from selectivenet_for_semantic_segmentation_binary_amd import _lib as K
-from tests.test_gpu_kernels import bn_fold, check_bnb_sums, gen, nchw, nhwc, rel
+from tests.test_gpu_kernels import bn_fold, check_bnb_sums, check_signed_inputs, gen, nchw, nhwc, rel
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -50,9 +50,15 @@ def pack_convT_bf16(wt):
 ])
 def test_convT_bf16_fwd(cin, cout, n, h, w, convt_ring):
     convt_ring(0)  # (the resident-weight kernel; the ring kernel: test_convT_bf16_ring_matches_resident)
+    convT_bf16_fwd_case(cin, cout, n, h, w)
+
+
+def convT_bf16_fwd_case(cin, cout, n, h, w, signed=False):
     x = gen(n, cin, h, w, seed=61).to(BF)
-    s, t = bn_fold(cin, 62)
+    s, t = bn_fold(cin, 62, signed)
     a = torch.relu(x.float() * s.view(1, -1, 1, 1) + t.view(1, -1, 1, 1)).to(BF)  # the stager's bf16 operand
+    if signed:
+        check_signed_inputs(s, a.float())
     wt = gen(cin, cout, 2, 2, seed=63, scale=0.05).to(BF)
     b = gen(cout, seed=64)
     ref = F.conv_transpose2d(a.double(), wt.double(), b.double(), stride=2)

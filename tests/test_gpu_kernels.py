@@ -81,10 +81,56 @@ def gen(*shape, seed=0, scale=1.0):
     return torch.randn(*shape, generator=g) * scale
 
 
-def bn_fold(c, seed):
+def signed_gamma(c, seed):
+    """N(0, 1) per channel as trained networks have them: both signs and exact zeros. Channels [0, 4) all
+    negative (a whole 4-channel vector group), [4, 8) exactly 0.0, one more exact zero at a seeded position."""
+    g = gen(c, seed=seed)
+    g[:4] = -(g[:4].abs() + 0.05)
+    g[4:8] = 0.0
+    g[8 + int(torch.randint(c - 8, (1,), generator=torch.Generator().manual_seed(seed)))] = 0.0
+    return g
+
+
+def bn_fold(c, seed, signed=False):
+    """Folded BatchNorm (scale, shift). signed: signed_gamma scales and shift ~ 0.5 N(0, 1), so the zero-scale
+    channels are constant-positive in some places and dead in others."""
+    if signed:
+        return signed_gamma(c, seed), gen(c, seed=seed + 1) * 0.5
     scale = gen(c, seed=seed).abs() + 0.5
     shift = gen(c, seed=seed + 1) * 0.3
     return scale, shift
+
+
+def bn_state(c, seed, signed=False):
+    """One BatchNorm layer's state for the backward tests, all derived from one gamma so that the ReLU mask
+    (scale) and k0 = coef[0] carry the same sign, as in training: gamma, beta, mean, invstd > 0,
+    scale = gamma*invstd, shift = beta - mean*scale, k0 = gamma*invstd (CPU fp32 tensors)."""
+    gamma = signed_gamma(c, seed) if signed else gen(c, seed=seed).abs() + 0.5
+    beta = gen(c, seed=seed + 1) * (0.5 if signed else 0.3)
+    mean, invstd = gen(c, seed=seed + 2) * 0.1, gen(c, seed=seed + 3).abs() + 0.5
+    scale = gamma * invstd
+    return dict(gamma=gamma, beta=beta, mean=mean, invstd=invstd, scale=scale, shift=beta - mean * scale,
+                k0=gamma * invstd)
+
+
+def check_signed_inputs(scale, act):
+    """Conditions a signed case asserts on its own inputs before it looks at the kernel: at least 25 % of the
+    channels have a negative scale, and the reference's ReLU (act = relu(v*scale + shift)) is active on 10 %
+    to 90 % of its elements."""
+    neg = float((scale < 0).float().mean())
+    active = float((act > 0).float().mean())
+    assert neg >= 0.25, neg
+    assert 0.1 <= active <= 0.9, active
+
+
+def bnb_operands(c, seed, signed=False):
+    """Device operands of a BN-backward sums epilogue: (scale, shift, mean, invstd). The unsigned form is the
+    recipe the data-gradient tests have always used (seeds seed .. seed + 3)."""
+    if signed:
+        st = bn_state(c, seed, True)
+        return tuple(st[k].to(DEV) for k in ("scale", "shift", "mean", "invstd"))
+    return ((gen(c, seed=seed).abs() + 0.5).to(DEV), (gen(c, seed=seed + 1) * 0.3).to(DEV),
+            (gen(c, seed=seed + 2) * 0.1).to(DEV), (gen(c, seed=seed + 3).abs() + 0.5).to(DEV))
 
 
 def pack(w, dt=torch.float32):
@@ -114,17 +160,23 @@ def test_conv3x3_fwd_stats(cin0, cin1, cout, n, h, w, xform, wgs, halo_wgs):
     """wgs = 3: the persistent multi-chunk halo kernel with 3 workgroup rows, so every workgroup
     walks several (unevenly many) tiles and accumulates its statistics over them."""
     halo_wgs(wgs)
+    conv3x3_fwd_stats_case(cin0, cin1, cout, n, h, w, xform)
+
+
+def conv3x3_fwd_stats_case(cin0, cin1, cout, n, h, w, xform, signed=False):
     x0 = gen(n, cin0, h, w, seed=1)
     x1 = gen(n, cin1, h, w, seed=2) if cin1 else None
     wt = gen(cout, cin0 + cin1, 3, 3, seed=3, scale=0.05)
-    s0, t0 = bn_fold(cin0, 10)
-    s1, t1 = bn_fold(cin1, 12) if cin1 else (None, None)
+    s0, t0 = bn_fold(cin0, 10, signed)
+    s1, t1 = bn_fold(cin1, 12, signed) if cin1 else (None, None)
     # reference: transform (BN fold + relu) applied to source 1 only when it is a "skip" source
     a0 = torch.relu(x0 * s0.view(1, -1, 1, 1) + t0.view(1, -1, 1, 1)) if xform else x0
     a = a0
     if cin1:
         a1 = torch.relu(x1 * s1.view(1, -1, 1, 1) + t1.view(1, -1, 1, 1))
         a = torch.cat((a0, a1), 1)
+    if signed:
+        check_signed_inputs(torch.cat((s0, s1)) if cin1 else s0, a)
     ref = F.conv2d(a, wt, padding=1)
     fwd, _, kpad = pack(wt)
     d = lambda t: t.to(DEV).contiguous()  # noqa: E731
@@ -170,6 +222,10 @@ def test_conv3x3_dgrad(cin, cout, split, h, w, wgs, halo_wgs, gather_wgs):
     row: one workgroup walks every tile and accumulates the column / BN-backward sums over them."""
     halo_wgs(wgs)
     gather_wgs(wgs - 2 if wgs else -1)
+    conv3x3_dgrad_case(cin, cout, split, h, w)
+
+
+def conv3x3_dgrad_case(cin, cout, split, h, w, signed=False):
     n = 6 if h == 8 else 2
     wt = gen(cout, cin, 3, 3, seed=6, scale=0.05)
     dy = gen(n, cout, h, w, seed=7)
@@ -194,8 +250,9 @@ def test_conv3x3_dgrad(cin, cout, split, h, w, wgs, halo_wgs, gather_wgs):
         dx = torch.empty(M, cin, device=DEV)
         # with the fused BatchNorm-backward sums of the producing layer (y, folded BN, batch stats)
         yprev = gen(M, cin, seed=42).to(DEV)
-        sc, sh = (gen(cin, seed=43).abs() + 0.5).to(DEV), (gen(cin, seed=44) * 0.3).to(DEV)
-        mean, invstd = (gen(cin, seed=45) * 0.1).to(DEV), (gen(cin, seed=46).abs() + 0.5).to(DEV)
+        sc, sh, mean, invstd = bnb_operands(cin, 43, signed)
+        if signed:
+            check_signed_inputs(sc, torch.relu(yprev * sc + sh))
         slab = torch.empty(rows, 3, cin, device=DEV)
         ep = K.Epilogue(K.ptr(dx), None, None, None, K.EP_PLAIN, 0)
         ep.bnb = K.BnBwdStats(K.ptr(yprev), K.ptr(sc), K.ptr(sh), K.ptr(mean), K.ptr(invstd), K.ptr(slab))
@@ -215,14 +272,20 @@ def test_conv3x3_dgrad(cin, cout, split, h, w, wgs, halo_wgs, gather_wgs):
 def test_conv3x3_wgrad(cin0, cin1, cout, xform, small, h, w):
     """fp32 weight gradient through both entry points: selunet_gemm_wgrad (fp32 atomics) and the
     deterministic split-partials path selunet_gemm_wgrad_ws (fixed-order reduction)."""
+    conv3x3_wgrad_case(cin0, cin1, cout, xform, small, h, w)
+
+
+def conv3x3_wgrad_case(cin0, cin1, cout, xform, small, h, w, signed=False):
     n = 2
     x0 = gen(n, cin0, h, w, seed=9)
     x1 = gen(n, cin1, h, w, seed=10) if cin1 else None
-    s0, t0 = bn_fold(cin0, 20)
-    s1, t1 = bn_fold(cin1, 22) if cin1 else (None, None)
+    s0, t0 = bn_fold(cin0, 20, signed)
+    s1, t1 = bn_fold(cin1, 22, signed) if cin1 else (None, None)
     a = torch.relu(x0 * s0.view(1, -1, 1, 1) + t0.view(1, -1, 1, 1)) if xform else x0
     if cin1:
         a = torch.cat((a, torch.relu(x1 * s1.view(1, -1, 1, 1) + t1.view(1, -1, 1, 1))), 1)
+    if signed:
+        check_signed_inputs(torch.cat((s0, s1)) if cin1 else s0, a)
     cin = cin0 + cin1
     wt = gen(cout, cin, 3, 3, seed=11, scale=0.05).requires_grad_()
     dy = gen(n, cout, h, w, seed=12)
@@ -252,6 +315,14 @@ def test_conv3x3_wgrad(cin0, cin1, cout, xform, small, h, w):
         det = wgrad_ws(gp, gq, packed, dtype=K.F32)
         K.call("selunet_unpack_conv3x3_grad", K.ptr(det), cout, cin, ld, K.ptr(out), K.stream_ptr())
         assert rel(out.cpu(), ref) < TOL
+        # ... and the split reduction writing the Conv2d layout directly (selunet_gemm_wgrad_ws_to)
+        wsb = K.query("selunet_gemm_wgrad_ws_bytes", gp, gq, K.F32)
+        if wsb > 0:
+            ws = torch.empty(wsb // 4, device=DEV)
+            to = torch.full_like(out, float("nan"))
+            K.call("selunet_gemm_wgrad_ws_to", gp, gq, None, K.ptr(ws), wsb, K.WG_CONV3X3, K.ptr(to), K.F32,
+                   K.stream_ptr())
+            assert rel(to.cpu(), ref) < TOL
 
 
 @pytest.mark.parametrize("cin,cout", [(512, 256), (128, 64)])
@@ -260,10 +331,16 @@ def test_convT_fwd_bwd(cin, cout, gwgs, gather_wgs):
     """4 row tiles (the last one ragged): one tile per workgroup (0), every tile in one workgroup
     (3), two tiles per workgroup (16 at 1024 columns) and the default persistent launch."""
     gather_wgs(gwgs)
+    convT_fwd_bwd_case(cin, cout)
+
+
+def convT_fwd_bwd_case(cin, cout, signed=False):
     n, h, w = 2, 13, 18
     x = gen(n, cin, h, w, seed=13)
-    s, t = bn_fold(cin, 30)
+    s, t = bn_fold(cin, 30, signed)
     a = torch.relu(x * s.view(1, -1, 1, 1) + t.view(1, -1, 1, 1)).requires_grad_()
+    if signed:
+        check_signed_inputs(s, a.detach())
     wt = gen(cin, cout, 2, 2, seed=14, scale=0.05).requires_grad_()
     b = gen(cout, seed=15).requires_grad_()
     y = F.conv_transpose2d(a, wt, b, stride=2)
@@ -297,6 +374,14 @@ def test_convT_fwd_bwd(cin, cout, gwgs, gather_wgs):
                    dtype=K.F32)  # split partials + fixed-order reduction
     K.call("selunet_unpack_convT_grad", K.ptr(det), cin, cout, K.ptr(gwd), K.stream_ptr())
     assert rel(gwd.cpu(), gw) < TOL
+    # ... and the split reduction writing the ConvTranspose2d layout directly (selunet_gemm_wgrad_ws_to)
+    gp, gq = K.gather(n, h, w, 1, K.source(xd, cin, sd, td)), K.gather(n, h, w, 4, K.source(dud, cout))
+    wsb = K.query("selunet_gemm_wgrad_ws_bytes", gp, gq, K.F32)
+    if wsb > 0:
+        ws = torch.empty(wsb // 4, device=DEV)
+        to = torch.full_like(gwd, float("nan"))
+        K.call("selunet_gemm_wgrad_ws_to", gp, gq, None, K.ptr(ws), wsb, K.WG_CONVT, K.ptr(to), K.F32, K.stream_ptr())
+        assert rel(to.cpu(), gw) < TOL
     Mu = n * 4 * h * w
     rows = K.query("selunet_channel_slab_rows", Mu)
     slab = torch.empty(rows, cout, device=DEV)
@@ -353,18 +438,24 @@ def check_bnb_sums(slab, da, y, scale, shift, mean, invstd, tol=1e-5):
 
 
 def test_bn_forward_backward_against_torch():
+    bn_forward_backward_case()
+
+
+def bn_forward_backward_case(signed=False):
     n, c, h, w = 4, 128, 8, 8
     M = n * h * w
     yr = gen(n, c, h, w, seed=20) * 2 + 0.5         # pre-BN conv output without bias
     bias = gen(c, seed=21) * 0.1
-    gamma = gen(c, seed=22).abs() + 0.5
-    beta = gen(c, seed=23) * 0.2
+    gamma = signed_gamma(c, 22) if signed else gen(c, seed=22).abs() + 0.5
+    beta = gen(c, seed=23) * (0.5 if signed else 0.2)
     rm0, rv0 = gen(c, seed=24) * 0.1, gen(c, seed=25).abs() + 0.5
     yb = (yr + bias.view(1, -1, 1, 1)).requires_grad_()
     gam = gamma.clone().requires_grad_()
     bet = beta.clone().requires_grad_()
     rm, rv = rm0.clone(), rv0.clone()
     z = torch.relu(F.batch_norm(yb, rm, rv, gam, bet, training=True, momentum=0.1, eps=1e-5))
+    if signed:
+        check_signed_inputs(gamma, z.detach())
     dz = gen(*z.shape, seed=26)
     g_y, g_gam, g_bet = torch.autograd.grad(z, (yb, gam, bet), dz)
     d = lambda t_: t_.to(DEV).contiguous()  # noqa: E731
@@ -576,10 +667,14 @@ def test_conv3x3_bf16_fwd_wgrad(cin0, cin1, cout, small, h, w, wgs, halo_wgs):
     """bf16 operands, fp32 accumulation: compared with fp32 torch on the same bf16-rounded data
     (sizes >= 16 take the halo-tiled kernels, incl. partial edge tiles)."""
     halo_wgs(wgs)
+    conv3x3_bf16_fwd_wgrad_case(cin0, cin1, cout, small, h, w)
+
+
+def conv3x3_bf16_fwd_wgrad_case(cin0, cin1, cout, small, h, w, signed=False):
     n = 2
     x0 = _bf(gen(n, cin0, h, w, seed=40))
     x1 = _bf(gen(n, cin1, h, w, seed=41)) if cin1 else None
-    s0, t0 = bn_fold(cin0, 42)
+    s0, t0 = bn_fold(cin0, 42, signed)
     cin = cin0 + cin1
     wt = _bf(gen(cout, cin, 3, 3, seed=43, scale=0.05))
     dy = _bf(gen(n, cout, h, w, seed=44))
@@ -590,6 +685,8 @@ def test_conv3x3_bf16_fwd_wgrad(cin0, cin1, cout, small, h, w, wgs, halo_wgs):
         srcs = [K.source(keep[0], cin0, layout=1)]
     else:
         a = _bf(torch.relu(x0 * s0.view(1, -1, 1, 1) + t0.view(1, -1, 1, 1)))
+        if signed:
+            check_signed_inputs(s0, a)
         keep = [d(nhwc(x0)).bfloat16(), d(s0), d(t0)]
         srcs = [K.source(keep[0], cin0, keep[1], keep[2])]
         if cin1:
@@ -614,6 +711,14 @@ def test_conv3x3_bf16_fwd_wgrad(cin0, cin1, cout, small, h, w, wgs, halo_wgs):
     gwd = torch.empty(cout, cin, 3, 3, device=DEV)
     K.call("selunet_unpack_conv3x3_grad", K.ptr(packed), cout, cin, ld, K.ptr(gwd), K.stream_ptr())
     assert rel(gwd.cpu(), gw) < 1e-3  # inputs exactly bf16, fp32 accumulation
+    # ... and the split reduction writing the Conv2d layout directly (selunet_gemm_wgrad_ws_to)
+    wsb = K.query("selunet_gemm_wgrad_ws_bytes", gp, gq, K.BF16)
+    if wsb > 0 and not small:
+        ws = torch.empty(wsb // 4, device=DEV)
+        to = torch.full_like(gwd, float("nan"))
+        K.call("selunet_gemm_wgrad_ws_to", gp, gq, None, K.ptr(ws), wsb, K.WG_CONV3X3, K.ptr(to), K.BF16,
+               K.stream_ptr())
+        assert rel(to.cpu(), gw) < 1e-3
 
 
 @pytest.mark.parametrize("n,h,w,cin,cout", [(2, 4, 6, 256, 128), (4, 16, 24, 128, 64), (3, 10, 14, 512, 256),
@@ -681,13 +786,21 @@ def test_first_conv_wgrad_bn_fused(dt, cin, n, h, w):
     """selunet_first_conv_wgrad_bn (encoder_layer_1_1's BN+ReLU backward formed while staging) against
     selunet_bn_bwd_apply + selunet_first_conv_wgrad on the same dA, y and coefficients: the same dy per
     element, so the same partial sums (fp32: to rounding of the MFMA order; bf16: dy rounded alike)."""
+    first_conv_wgrad_bn_case(dt, cin, n, h, w)
+
+
+def first_conv_wgrad_bn_case(dt, cin, n, h, w, signed=False):
+    """signed: also against the fp64 weight gradient of the fp64 dy = [y*scale+shift > 0] k0 dz - k1 - k2 xhat
+    (independent of the apply kernel), to the first-conv weight gradient's tolerance."""
     M, co = n * h * w, 64
     x = gen(n, cin, h, w, seed=70).to(DEV).contiguous()
     dz = gen(M, co, seed=71).to(dt).to(DEV)
     y = gen(M, co, seed=72).to(dt).to(DEV)
-    sc, sh = (gen(co, seed=73).abs() + 0.5).to(DEV), (gen(co, seed=74) * 0.3).to(DEV)
-    mean, invstd = (gen(co, seed=75) * 0.1).to(DEV), (gen(co, seed=76).abs() + 0.5).to(DEV)
+    sc, sh, mean, invstd = bnb_operands(co, 73, signed)
     coef = (gen(3, co, seed=77) * 0.2).to(DEV).contiguous()
+    if signed:
+        coef[0] = bn_state(co, 73, True)["k0"].to(DEV)
+        check_signed_inputs(sc, torch.relu(y.float() * sc + sh))
     dy = torch.empty(M, co, dtype=dt, device=DEV)
     K.call("selunet_bn_bwd_apply", K.ptr(dz), K.ptr(y), M, co, K.ptr(sc), K.ptr(sh), K.ptr(mean), K.ptr(invstd),
            K.ptr(coef), K.ptr(dy), K.dtype_code(dt), K.stream_ptr())
@@ -699,6 +812,17 @@ def test_first_conv_wgrad_bn_fused(dt, cin, n, h, w):
     torch.cuda.synchronize()
     r, g = ref.double().sum(0).cpu(), got.double().sum(0).cpu()
     assert rel(g, r) < (1e-6 if dt == torch.float32 else 1e-5)
+    if signed:
+        y64, dz64 = y.double().cpu(), dz.double().cpu()
+        k = coef.double().cpu()
+        xh = (y64 - mean.double().cpu()) * invstd.double().cpu()
+        dy64 = (y64 * sc.double().cpu() + sh.double().cpu() > 0).double() * k[0] * dz64 - k[1] - k[2] * xh
+        dyq = dy64.to(dt).double()  # what the staging holds
+        ref_w = torch.nn.grad.conv2d_weight(x.double().cpu(), (co, cin, 3, 3), nchw(dyq, n, h, w), padding=1)
+        packed = got.double().sum(0).float().contiguous()
+        gw = torch.empty(co, cin, 3, 3, device=DEV)
+        K.call("selunet_unpack_conv3x3_grad", K.ptr(packed), co, cin, 32, K.ptr(gw), K.stream_ptr())
+        assert rel(gw.cpu(), ref_w) < (TOL if dt == torch.float32 else 1e-2)
 
 
 @pytest.mark.parametrize("cin0,cin1,cout,n,h,w", [
@@ -715,12 +839,18 @@ def test_conv3x3_bf16_persist_fwd_stats(cin0, cin1, cout, n, h, w, wgs, variant,
     wgs = 3 makes every workgroup walk several tiles; variant: a kernel-selection option set for the test."""
     halo_wgs(wgs)
     kernel_option(variant)
+    conv3x3_bf16_persist_fwd_stats_case(cin0, cin1, cout, n, h, w)
+
+
+def conv3x3_bf16_persist_fwd_stats_case(cin0, cin1, cout, n, h, w, signed=False):
     x0 = _bf(gen(n, cin0, h, w, seed=60))
     x1 = _bf(gen(n, cin1, h, w, seed=61)) if cin1 else None
-    s0, t0 = bn_fold(cin0, 62)
+    s0, t0 = bn_fold(cin0, 62, signed)
     wt = _bf(gen(cout, cin0 + cin1, 3, 3, seed=63, scale=0.05))
     d = lambda t_: t_.to(DEV).contiguous()  # noqa: E731
     a = _bf(torch.relu(x0 * s0.view(1, -1, 1, 1) + t0.view(1, -1, 1, 1)))
+    if signed:
+        check_signed_inputs(s0, a)
     keep = [d(nhwc(x0)).bfloat16(), d(s0), d(t0)]
     srcs = [K.source(keep[0], cin0, keep[1], keep[2])]
     if cin1:
@@ -753,6 +883,10 @@ def test_conv3x3_bf16_persist_dgrad(cin, cout, split, h, w, wgs, variant, halo_w
     and the torch.cat split with the ConvTranspose2d bias column sums."""
     halo_wgs(wgs)
     kernel_option(variant)
+    conv3x3_bf16_persist_dgrad_case(cin, cout, split, h, w)
+
+
+def conv3x3_bf16_persist_dgrad_case(cin, cout, split, h, w, signed=False):
     n = 2
     wt = _bf(gen(cout, cin, 3, 3, seed=64, scale=0.05))
     dy = _bf(gen(n, cout, h, w, seed=65))
@@ -775,8 +909,9 @@ def test_conv3x3_bf16_persist_dgrad(cin, cout, split, h, w, wgs, variant, halo_w
     else:
         dx = torch.empty(M, cin, dtype=torch.bfloat16, device=DEV)
         yprev = gen(M, cin, seed=67).to(DEV).bfloat16()
-        sc, sh = (gen(cin, seed=68).abs() + 0.5).to(DEV), (gen(cin, seed=69) * 0.3).to(DEV)
-        mean, invstd = (gen(cin, seed=70) * 0.1).to(DEV), (gen(cin, seed=71).abs() + 0.5).to(DEV)
+        sc, sh, mean, invstd = bnb_operands(cin, 68, signed)
+        if signed:
+            check_signed_inputs(sc, torch.relu(yprev.float() * sc + sh))
         slab = torch.empty(rows, 3, cin, device=DEV)
         ep = K.Epilogue(K.ptr(dx), None, None, None, K.EP_PLAIN, 0)
         ep.bnb = K.BnBwdStats(K.ptr(yprev), K.ptr(sc), K.ptr(sh), K.ptr(mean), K.ptr(invstd), K.ptr(slab))

@@ -319,10 +319,50 @@ def test_step_against_oracle_shapes(input_type, n, h, w, selective):
     as in check_step: relative-L2 error against the oracle's fp64 run within tests/_golden.grad_bound
     of the oracle fp32 run's own error (ReLU / max-pool near-ties route fp32
     gradients differently under any change of summation order)."""
+    step_against_oracle(input_type, n, h, w, selective, L.seeded_params(3, input_type, selective))
+
+
+def drifted_params(input_type, selective, seed=77):
+    """A parameter state as training leaves it, from one numpy recipe for the net and the oracle: every BN gamma
+    ~ N(0, 1) with 5 % exact zeros, every BN beta ~ N(0, 0.5), every 3x3 conv weight row scaled by 2^U(-6, 6) (the
+    per-row scales of the split-fp16 weight pack; large and small batch variances)."""
+    p = L.seeded_params(3, input_type, selective)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    for name, _, co in L.CBR_LAYERS:
+        gamma = rng.standard_normal(co)
+        gamma[rng.random(co) < 0.05] = 0.0
+        p[f"{name}.1.weight"] = gamma.astype(np.float32)
+        p[f"{name}.1.bias"] = (0.5 * rng.standard_normal(co)).astype(np.float32)
+        w = p[f"{name}.0.weight"]
+        p[f"{name}.0.weight"] = (w * 2.0 ** rng.uniform(-6, 6, size=(co, 1, 1, 1))).astype(np.float32)
+    return p
+
+
+_ORACLE_CACHE = {}
+
+
+@pytest.mark.parametrize("input_type,n,h,w,selective", [
+    ("RGB", 2, 32, 32, True),
+    ("RGB", 2, 40, 56, True),    # pyramid 40x56, 20x28, 10x14, 5x7: split-fp16 eligibility flips, ragged tiles
+    ("RGB", 3, 24, 24, False),
+])
+@pytest.mark.parametrize("x2", ["1", "0"])  # the default split-fp16 path, the exact-fp32 path
+def test_step_against_oracle_drifted_state(input_type, n, h, w, selective, x2, monkeypatch):
+    """test_step_against_oracle_shapes from a drifted parameter state (drifted_params: BN gammas of both signs
+    and exactly zero, betas of either sign, conv rows over a 2^12 range of scales) instead of the seeded one
+    (gamma in [0.6, 1.4]), with the same bounds, and the running statistics after the step against the oracle's
+    (rtol 1e-4, atol 1e-5, as check_step's strict step). The oracle's own fp32 and fp64 runs agree on this
+    state to rounding except where one ReLU / max-pool kink flips, which grad_bound's ensemble terms absorb."""
+    monkeypatch.setenv("SELUNET_X2", x2)  # read when the engine is built
+    step_against_oracle(input_type, n, h, w, selective, drifted_params(input_type, selective), buffers=True,
+                        cache_key=("drifted", input_type, n, h, w, selective))
+
+
+def step_against_oracle(input_type, n, h, w, selective, p, buffers=False, cache_key=None):
+    """One training step of the HIP path from parameters p (key -> ndarray) against the oracle from the same p."""
     x, lab = make_batch(n, max(h, w), seed=11)
     x = np.ascontiguousarray(x[:, :L.input_channels(input_type), :h, :w])
     lab = np.ascontiguousarray(lab[:, :h, :w])
-    p = L.seeded_params(3, input_type, selective)
     net = S.UNet_B(input_type, selective=selective)
     with torch.no_grad():
         for k, t in net.named_parameters():
@@ -339,12 +379,15 @@ def test_step_against_oracle_shapes(input_type, n, h, w, selective):
     loss.backward()
     torch.cuda.synchronize()
 
+    obuf = {}
+
     def oracle(dt, xin=x):
-        params, buffers = O.make_state(3, input_type, selective)
-        params = {k: v.detach().to(dt).requires_grad_() for k, v in params.items()}
-        buffers = {k: (v.to(dt) if v.is_floating_point() else v) for k, v in buffers.items()}
+        params, bufs = O.make_state(3, input_type, selective)
+        params = {k: torch.tensor(p[k]).to(dt).requires_grad_() for k in params}
+        bufs = {k: (v.to(dt) if v.is_floating_point() else v) for k, v in bufs.items()}
         xo, lo = torch.tensor(xin, dtype=dt), torch.tensor(lab, dtype=dt)
-        ro = O.forward(params, buffers, xo, selective, training=True)
+        ro = O.forward(params, bufs, xo, selective, training=True)
+        obuf[dt] = bufs
         if selective:
             o2, s2, a2 = ro
             sl2, _ = O.selective_risk_b_stable(o2, s2, lo, lamb=2)
@@ -354,9 +397,36 @@ def test_step_against_oracle_shapes(input_type, n, h, w, selective):
         l2.backward()
         return float(l2.detach()), {k: v.grad.double() for k, v in params.items()}
 
-    loss32, g32 = oracle(torch.float32)
-    _, g64 = oracle(torch.float64)
+    if cache_key in _ORACLE_CACHE:  # (the same reference for both convolution paths)
+        loss32, g32, g64, ens, b32 = _ORACLE_CACHE[cache_key]
+    else:
+        loss32, g32, g64, ens, b32 = oracle_reference(oracle, obuf, x)
+        if cache_key is not None:
+            _ORACLE_CACHE[cache_key] = (loss32, g32, g64, ens, b32)
     assert abs(loss.item() - loss32) < 1e-4 * max(1.0, abs(loss32))
+    fails = []
+    for k, q in net.named_parameters():
+        if k in PRE_BN_BIAS:  # cancels inside training-mode BN: zero gradient on both sides
+            continue
+        assert bool(torch.isfinite(q.grad).all()), k
+        nrm = float(g64[k].norm()) + 1e-30
+        err = float((q.grad.cpu().double() - g64[k]).norm()) / nrm
+        err_ref = float((g32[k] - g64[k]).norm()) / nrm
+        if not err <= G.grad_bound(err_ref, ens[k]):
+            fails.append((k, err, err_ref, ens[k]))
+    assert not fails, fails
+    if buffers:
+        for k, v in net.named_buffers():
+            if "running" in k:
+                np.testing.assert_allclose(v.cpu().numpy(), b32[k].numpy(), rtol=1e-4, atol=1e-5, err_msg=k)
+
+
+def oracle_reference(oracle, obuf, x):
+    """The oracle's fp32 loss and gradients, its fp64 gradients, its own fp32 error under rounding-level
+    perturbations (the e_ens of tests/_golden.grad_bound) and its buffers after the unperturbed fp32 step."""
+    loss32, g32 = oracle(torch.float32)
+    b32 = {k: v.clone() for k, v in obuf[torch.float32].items()}
+    _, g64 = oracle(torch.float64)
     # the oracle's own fp32 error on 4 rounding-level perturbations of the input (the e_ens of
     # tests/_golden.grad_bound)
     ens = {}
@@ -377,10 +447,4 @@ def test_step_against_oracle_shapes(input_type, n, h, w, selective):
             _, p32 = oracle(torch.float32)
         for k in g64:
             ens[k] = max(ens[k], float((p32[k] - g64[k]).norm() / (g64[k].norm() + 1e-30)))
-    for k, q in net.named_parameters():
-        if k in PRE_BN_BIAS:  # cancels inside training-mode BN: zero gradient on both sides
-            continue
-        nrm = float(g64[k].norm()) + 1e-30
-        err = float((q.grad.cpu().double() - g64[k]).norm()) / nrm
-        err_ref = float((g32[k] - g64[k]).norm()) / nrm
-        assert err <= G.grad_bound(err_ref, ens[k]), (k, err, err_ref, ens[k])
+    return loss32, g32, g64, ens, b32

@@ -11,7 +11,8 @@ import torch
 import torch.nn.functional as F
 
 from selectivenet_for_semantic_segmentation_binary_amd import _lib as K
-from tests.test_gpu_kernels import bn_fold, check_bnb_sums, gen, halo_wgs, nchw, nhwc, rel  # noqa: F401
+from tests.test_gpu_kernels import (bn_fold, bnb_operands, check_bnb_sums, check_signed_inputs, gen,  # noqa: F401
+                                    halo_wgs, nchw, nhwc, rel)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -69,14 +70,20 @@ def test_wino_eligibility():
 @pytest.mark.parametrize("wgs", [0, 3])
 def test_wino_fwd_stats(cin0, cin1, cout, n, h, w, xform, wgs, halo_wgs):
     halo_wgs(wgs)
+    wino_fwd_stats_case(cin0, cin1, cout, n, h, w, xform)
+
+
+def wino_fwd_stats_case(cin0, cin1, cout, n, h, w, xform, signed=False):
     x0 = gen(n, cin0, h, w, seed=1)
     x1 = gen(n, cin1, h, w, seed=2) if cin1 else None
     wt = gen(cout, cin0 + cin1, 3, 3, seed=3, scale=0.05)
-    s0, t0 = bn_fold(cin0, 10)
+    s0, t0 = bn_fold(cin0, 10, signed)
     a = torch.relu(x0 * s0.view(1, -1, 1, 1) + t0.view(1, -1, 1, 1)) if xform else x0
     if cin1:
-        s1, t1 = bn_fold(cin1, 12)
+        s1, t1 = bn_fold(cin1, 12, signed)
         a = torch.cat((a, torch.relu(x1 * s1.view(1, -1, 1, 1) + t1.view(1, -1, 1, 1))), 1)
+    if signed:
+        check_signed_inputs(torch.cat((s0, s1)) if cin1 else s0, a)
     ref = F.conv2d(a.double(), wt.double(), padding=1)
     assert K.query("selunet_conv3x3_wino_ok", h, w, cin0 + cin1, cin0, cout) == 1
     u, _ = pack_wino(wt, dgrad=False)
@@ -106,6 +113,10 @@ def test_wino_fwd_stats(cin0, cin1, cout, n, h, w, xform, wgs, halo_wgs):
 @pytest.mark.parametrize("wgs", [0, 3])
 def test_wino_dgrad(cin, cout, split, h, w, wgs, halo_wgs):
     halo_wgs(wgs)
+    wino_dgrad_case(cin, cout, split, h, w)
+
+
+def wino_dgrad_case(cin, cout, split, h, w, signed=False):
     n = 2
     wt = gen(cout, cin, 3, 3, seed=6, scale=0.05)
     dy = gen(n, cout, h, w, seed=7)
@@ -127,8 +138,9 @@ def test_wino_dgrad(cin, cout, split, h, w, wgs, halo_wgs):
     else:
         dx = torch.empty(M, cin, device=DEV)
         yprev = gen(M, cin, seed=42).to(DEV)
-        sc, sh = (gen(cin, seed=43).abs() + 0.5).to(DEV), (gen(cin, seed=44) * 0.3).to(DEV)
-        mean, invstd = (gen(cin, seed=45) * 0.1).to(DEV), (gen(cin, seed=46).abs() + 0.5).to(DEV)
+        sc, sh, mean, invstd = bnb_operands(cin, 43, signed)
+        if signed:
+            check_signed_inputs(sc, torch.relu(yprev * sc + sh))
         slab = torch.empty(rows, 3, cin, device=DEV)
         ep = K.Epilogue(K.ptr(dx), None, None, None, K.EP_PLAIN, 0)
         ep.bnb = K.BnBwdStats(K.ptr(yprev), K.ptr(sc), K.ptr(sh), K.ptr(mean), K.ptr(invstd), K.ptr(slab))
@@ -159,18 +171,24 @@ def test_wino_wgrad(cin0, cin1, cout, xform, n, h, w):
     """fp32 Winograd weight gradient (conv3x3_wgrad_wino_f32_kernel + the plane reduction) through
     selunet_gemm_wgrad_ws_to (the Conv2d weight layout) and selunet_gemm_wgrad_ws (packed), against
     torch's conv2d weight gradient in fp64; the two entry points agree bit for bit."""
+    wino_wgrad_case(cin0, cin1, cout, xform, n, h, w)
+
+
+def wino_wgrad_case(cin0, cin1, cout, xform, n, h, w, signed=False):
     x0 = gen(n, cin0, h, w, seed=9)
-    s0, t0 = bn_fold(cin0, 20)
+    s0, t0 = bn_fold(cin0, 20, signed)
     a = torch.relu(x0 * s0.view(1, -1, 1, 1) + t0.view(1, -1, 1, 1)) if xform else x0
     d = lambda t: t.to(DEV).contiguous()  # noqa: E731
     keep = [d(nhwc(x0)), d(s0), d(t0)]
     srcs = [K.source(keep[0], cin0, keep[1] if xform else None, keep[2] if xform else None)]
     if cin1:
         x1 = gen(n, cin1, h, w, seed=10)
-        s1, t1 = bn_fold(cin1, 22)
+        s1, t1 = bn_fold(cin1, 22, signed)
         a = torch.cat((a, torch.relu(x1 * s1.view(1, -1, 1, 1) + t1.view(1, -1, 1, 1))), 1)
         keep += [d(nhwc(x1)), d(s1), d(t1)]
         srcs.append(K.source(keep[3], cin1, keep[4], keep[5]))
+    if signed:
+        check_signed_inputs(torch.cat((s0, s1)) if cin1 else s0, a)
     cin = cin0 + cin1
     wt = gen(cout, cin, 3, 3, seed=11, scale=0.05).double().requires_grad_()
     dy = gen(n, cout, h, w, seed=12)

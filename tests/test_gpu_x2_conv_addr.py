@@ -30,7 +30,7 @@ import torch.nn.functional as F
 from selectivenet_for_semantic_segmentation_binary_amd import _lib as K
 from tests.test_gpu_bn_shift import check_shifted_sums, fp32_run, stat_tol
 from tests.test_gpu_kernels import bn_fold, check_bnb_sums, gen, nchw, nhwc, rel
-from tests.test_gpu_x2 import TOL, pack_x2
+from tests.test_gpu_x2 import SLACKS, TOL, pack_x2
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -114,6 +114,18 @@ def modes(cout):
 @pytest.mark.parametrize("source", SOURCES)
 @pytest.mark.parametrize("cin0,cin1,cout,n,h,w", SHAPES)
 def test_x2_conv_staging_addresses(cin0, cin1, cout, n, h, w, source):
+    staging_case(cin0, cin1, cout, n, h, w, source)
+
+
+@pytest.mark.parametrize("slack", SLACKS)
+@pytest.mark.parametrize("cin0,cin1,cout,n,h,w", [SHAPES[0], SHAPES[3]])
+def test_x2_conv_staging_addresses_loose_words(cin0, cin1, cout, n, h, w, slack):
+    """Both input range words multiplied by `slack` (as training's Samuelson bounds are above the real maximum):
+    same checks, same bounds."""
+    staging_case(cin0, cin1, cout, n, h, w, "bnrelu", slack=slack)
+
+
+def staging_case(cin0, cin1, cout, n, h, w, source, slack=1.0):
     c = case(cin0, cin1, cout, n, h, w, source)
     M = n * h * w
     assert K.query("selunet_conv3x3_x2_ok", h, w, cin0 + cin1, cin0, cout) == 1
@@ -129,11 +141,11 @@ def test_x2_conv_staging_addresses(cin0, cin1, cout, n, h, w, source):
     sc_keep = [d(c["s0"]), d(c["t0"])]
     srcs = [K.source(banded(nhwc(c["x0"]), w * cin0), cin0, sc_keep[0] if coef else None, sc_keep[1] if coef else None,
                      relu=source == "bnrelu")]
-    am0, am1 = torch.tensor([c["am0"]], device=DEV), None
+    am0, am1 = torch.tensor([c["am0"] * slack], device=DEV), None
     if cin1:
         sc_keep += [d(c["s1"]), d(c["t1"])]
         srcs.append(K.source(banded(nhwc(c["x1"]), w * cin1), cin1, sc_keep[2], sc_keep[3]))
-        am1 = torch.tensor([c["am1"]], device=DEV)
+        am1 = torch.tensor([c["am1"] * slack], device=DEV)
     u0, _ = pack_x2(c["wt"], dgrad=False)
     u = banded(u0, w * (cin0 + cin1))
     g = K.gather(n, h, w, 9, *srcs)
