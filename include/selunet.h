@@ -676,6 +676,24 @@ int selunet_prep_batch_mode(const uint8_t* img, const uint8_t* lab, const uint8_
 int selunet_seg_metrics(const float* out, const float* sel, const float* target, int64_t p,
                         float t_out, float t_sel, unsigned long long* counts, void* stream);
 
+/* Risk-coverage sweep: the counts of selunet_seg_metrics at k selection thresholds in one pass.
+ * bins: uint64 [(k+1)][5], caller-zeroed, accumulated across calls.
+ * bin b of a pixel = number of j in [0,k) with sel >= t_sel[j]
+ *   (t_sel: DEVICE array, ascending — the caller's duty —, duplicates and +-inf allowed;
+ *    NaN sel -> bin 0).
+ * bins[b] = {cm[0][0], cm[0][1], cm[1][0], cm[1][1], pixels}
+ *   cm[label][pred], pred = out >= t_out, label = (uint8)target, counted only when label < 2
+ *   (the rule of selunet_seg_metrics); `pixels` counts every pixel of the bin whatever its label.
+ * For every j the sum of bins[b] over b > j equals counts[0..4] of selunet_seg_metrics at
+ * t_sel[j], and the sum of `pixels` over all bins its counts[5]. Integer atomics only: the result
+ * does not depend on scheduling. EINVAL for a null pointer, p <= 0 or p > 2^40 (a 32-bit
+ * on-chip counter could overflow beyond), k outside [1, SELUNET_SWEEP_MAX], out / sel / target
+ * not 16-B aligned. */
+#define SELUNET_SWEEP_MAX 256
+int selunet_seg_metrics_sweep(const float* out, const float* sel, const float* target, int64_t p,
+                              float t_out, const float* t_sel, int32_t k,
+                              unsigned long long* bins, void* stream);
+
 /* ---- multi-GPU overlap probe (bench/tools only, not on the training path) ------
  * Stand-in for one bucketed RCCL all-reduce kernel on a single GPU: n_wg workgroups of 256 threads
  * reduce-copy dst[i] += src[i] over their slices of [0, n) (n % 4 == 0, 16-B aligned), repeatedly,

@@ -9,8 +9,11 @@
 //    prediction threshold, selection threshold, rejection count and the Evaluator's 2x2
 //    confusion matrix (utils/compute_metric.py:10-26) — as integer counts accumulated on the
 //    device, so the loop never copies the [N,H,W] outputs to the host.
+//  * selunet_seg_metrics_sweep: the same counts at up to 256 selection cut-offs in one pass (the
+//    risk-coverage curve), as a per-bin histogram the host suffix-sums.
 //
-// Both are HBM-bound byte/int work (no MFMA): 16-B coalesced loads, one pass over the data.
+// All are byte/int work (no MFMA) in one pass over the data with 16-B coalesced loads; at an eval
+// batch the metrics kernels are bound by their launch and their closing atomics, not by HBM.
 #include <algorithm>
 
 #include "common.h"
@@ -144,6 +147,99 @@ __global__ void seg_metrics_kernel(const float* __restrict__ out, const float* _
   if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(counts + 5, (unsigned long long)p);
 }
 
+// Risk-coverage sweep: seg_metrics_kernel's counts at k selection thresholds in one pass. With the
+// thresholds ascending, `sel >= t_sel[j]` is a prefix of the list, so a pixel belongs to one bin
+// b = #{j : sel >= t_sel[j]} in [0, k] and is selected at threshold j exactly when b > j: the
+// per-bin histogram, suffix-summed by the host, gives every threshold's counts.
+//
+// Per pixel one 32-bit LDS counter [bin][class], class = cm cell (label * 2 + pred) or 4 for a label
+// >= 2 (in `pixels` only). Trained selection scores cluster in a few bins, so same-address LDS
+// atomics are the hazard: each wave has a private histogram, and when a whole wave agrees on the
+// bin (a wave-uniform branch) it adds one ballot population count per class instead of 64 ones.
+constexpr int SWEEP_WAVES = IO_TPB / 64;
+constexpr int SWEEP_CLASSES = 5;
+// One workgroup per CU: every workgroup adds its bins to the same cache lines at the end, and those
+// requests are served one after the other (measured on 16 x 256 x 256 pixels, k = 11, uniform bins:
+// 12.2 us at 256 workgroups, 15.4 us at 512, 25.2 us at 1024).
+constexpr int SWEEP_GRID = 256;
+// A wave counts at most its share of p pixels into a 32-bit counter: ~p / (SWEEP_GRID * SWEEP_WAVES)
+// once the grid is capped, < 2^30 at this bound.
+constexpr int64_t SWEEP_MAX_PIXELS = (int64_t)1 << 40;
+
+// top: the largest power of two <= min(k, SELUNET_SWEEP_MAX - 1) (the first binary-search stride)
+__global__ __launch_bounds__(IO_TPB) void seg_metrics_sweep_kernel(
+    const float* __restrict__ out, const float* __restrict__ sel, const float* __restrict__ target, int64_t p,
+    float t_out, const float* __restrict__ t_sel, int k, int top, unsigned long long* __restrict__ bins) {
+  // NaN padding: `s >= NaN` is false, so the padded list keeps its true-prefix shape for s = +inf too
+  __shared__ float thr[SELUNET_SWEEP_MAX];
+  __shared__ unsigned hist[SWEEP_WAVES][(SELUNET_SWEEP_MAX + 1) * SWEEP_CLASSES];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int cells = (k + 1) * SWEEP_CLASSES;
+  for (int i = threadIdx.x; i < SELUNET_SWEEP_MAX; i += IO_TPB) thr[i] = i < k ? t_sel[i] : __builtin_nanf("");
+  for (int i = threadIdx.x; i < cells; i += IO_TPB)
+#pragma unroll
+    for (int wv = 0; wv < SWEEP_WAVES; ++wv) hist[wv][i] = 0;
+  __syncthreads();
+  unsigned* mine = hist[wave];
+
+  // the true-prefix length over thr[0 .. 2*top-2] by binary search, then the last entry on its own
+  // (k = 256 has 257 bins, one more than 8 halvings tell apart)
+  auto bin_of = [&](float s) {
+    int b = 0;
+    for (int st = top; st > 0; st >>= 1) b += s >= thr[b + st - 1] ? st : 0;
+    return b + (s >= thr[SELUNET_SWEEP_MAX - 1] ? 1 : 0);
+  };
+  auto class_of = [&](float o, float t) {
+    const int lab = (int)(uint8_t)t;  // as seg_metrics_kernel
+    return lab < 2 ? lab * 2 + (o >= t_out ? 1 : 0) : 4;
+  };
+  auto count = [&](int b, int cls) {
+    const unsigned long long active = __ballot(1);
+    const int b0 = __builtin_amdgcn_readfirstlane(b);
+    if (__ballot(b == b0) == active) {
+      // the wave agrees on the bin: one add per class present, by the lowest lane of that class
+      unsigned long long same = 0;
+#pragma unroll
+      for (int c = 0; c < SWEEP_CLASSES; ++c) {
+        const unsigned long long m = __ballot(cls == c);
+        same = cls == c ? m : same;
+      }
+      if (lane == __ffsll((long long)same) - 1) atomicAdd(&mine[b0 * SWEEP_CLASSES + cls], (unsigned)__popcll(same));
+    } else {
+      atomicAdd(&mine[b * SWEEP_CLASSES + cls], 1u);
+    }
+  };
+  const int64_t p4 = p >> 2;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < p4; i += stride) {
+    const f32x4 o = *reinterpret_cast<const f32x4*>(out + i * 4);
+    const f32x4 t = *reinterpret_cast<const f32x4*>(target + i * 4);
+    const f32x4 s = *reinterpret_cast<const f32x4*>(sel + i * 4);
+    int b[4];  // the four searches first: independent chains of dependent LDS reads
+#pragma unroll
+    for (int j = 0; j < 4; ++j) b[j] = bin_of(s[j]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) count(b[j], class_of(o[j], t[j]));
+  }
+  for (int64_t i = p4 * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < p; i += stride)
+    count(bin_of(sel[i]), class_of(out[i], target[i]));
+  __syncthreads();
+  // One thread per cell of bins, so that a wave's atomic covers 512 contiguous bytes: the workgroups
+  // all add to the same few cache lines, and device atomics on one line are served one request (a
+  // wave-instruction's share of the line) after the other. Integer atomics: the sums do not depend on
+  // the order the workgroups arrive in.
+  for (int i = threadIdx.x; i < cells; i += IO_TPB) {
+    unsigned long long s = 0;
+#pragma unroll
+    for (int wv = 0; wv < SWEEP_WAVES; ++wv) s += hist[wv][i];
+    if (i % SWEEP_CLASSES == 4)  // `pixels`: the other-label class plus the four cm cells of the bin
+      for (int d = 1; d < SWEEP_CLASSES; ++d)
+#pragma unroll
+        for (int wv = 0; wv < SWEEP_WAVES; ++wv) s += hist[wv][i - d];
+    if (s) atomicAdd(bins + i, s);
+  }
+}
+
 }  // namespace selunet
 
 using namespace selunet;
@@ -185,6 +281,24 @@ int selunet_seg_metrics(const float* out, const float* sel, const float* target,
   hipLaunchKernelGGL(seg_metrics_kernel, dim3(grid), dim3(IO_TPB), 0, as_stream(stream), out, sel, target, p, t_out,
                      t_sel, counts);
   return check_launch("seg_metrics");
+}
+
+int selunet_seg_metrics_sweep(const float* out, const float* sel, const float* target, int64_t p, float t_out,
+                              const float* t_sel, int32_t k, unsigned long long* bins, void* stream) {
+  SELUNET_REQUIRE(out && sel && target && t_sel && bins, "seg_metrics_sweep: null out, sel, target, t_sel or bins");
+  SELUNET_REQUIRE(p > 0 && p <= SWEEP_MAX_PIXELS, "seg_metrics_sweep: p must be in [1, 2^40] (got %lld)", (long long)p);
+  SELUNET_REQUIRE(k >= 1 && k <= SELUNET_SWEEP_MAX, "seg_metrics_sweep: k must be in [1, %d] (got %d)",
+                  SELUNET_SWEEP_MAX, k);
+  SELUNET_REQUIRE(((uintptr_t)out & 15) == 0 && ((uintptr_t)target & 15) == 0 && ((uintptr_t)sel & 15) == 0,
+                  "seg_metrics_sweep: inputs must be 16-B aligned");
+  SELUNET_REQUIRE(((uintptr_t)t_sel & 3) == 0 && ((uintptr_t)bins & 7) == 0,
+                  "seg_metrics_sweep: t_sel must be 4-B and bins 8-B aligned");
+  int top = 1;
+  while (top * 2 <= std::min(k, SELUNET_SWEEP_MAX - 1)) top *= 2;
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(p / 4 + 1, IO_TPB), SWEEP_GRID));
+  hipLaunchKernelGGL(seg_metrics_sweep_kernel, dim3(grid), dim3(IO_TPB), 0, as_stream(stream), out, sel, target, p,
+                     t_out, t_sel, k, top, bins);
+  return check_launch("seg_metrics_sweep");
 }
 
 }  // extern "C"

@@ -14,6 +14,10 @@ by construction) and read once at the end.
 Ensembles (several checkpoints, selective off, eval.py:185-199) average the per-model outputs on
 the GPU in the reference's order; with --ens_scale sigmoid the GPU's exp differs from numpy's by
 an ulp on some pixels (parity unpinned for that mode); None / clip / minmax are exact.
+Risk-coverage sweep (MI355X path only): --s_cut_off_sweep F [F ...] or --s_cut_off_steps N evaluates
+every selection cut-off of the list in the same single pass (`metrics.SelectiveSweep`, counts equal to
+a run with that --s_cut_off alone) and writes risk_coverage.json / .csv next to performance.json;
+--target_coverage C adds the largest cut-off of the list whose coverage is still >= C.
 A single process evaluates on the first id of --local_rank (the reference's DataParallel split
 of an eval batch changes nothing in eval mode).
 """
@@ -52,7 +56,28 @@ def parse_arguments(argv=None):
     parser.add_argument('--save_dir', type=str, default='./output', help='saving results')
     # ---- MI355X path options
     parser.add_argument('--compute_dtype', type=str, default='fp32', choices=['fp32', 'bf16'])
-    return parser.parse_args(argv)
+    sweep = parser.add_mutually_exclusive_group()
+    sweep.add_argument('--s_cut_off_sweep', type=float, nargs='+', default=None,
+                       help='selection cut-offs of a one-pass risk-coverage sweep')
+    sweep.add_argument('--s_cut_off_steps', type=int, default=None,
+                       help='N: sweep the N+1 cut-offs linspace(0, 1, N+1) (N <= 255)')
+    parser.add_argument('--target_coverage', type=float, default=None,
+                        help='with a sweep: report the largest cut-off whose coverage is >= this')
+    args = parser.parse_args(argv)
+    if args.s_cut_off_steps is not None and not 1 <= args.s_cut_off_steps <= 255:
+        parser.error('--s_cut_off_steps: N must be in [1, 255]')
+    if args.target_coverage is not None and sweep_cut_offs(args) is None:
+        parser.error('--target_coverage needs --s_cut_off_sweep or --s_cut_off_steps')
+    return args
+
+
+def sweep_cut_offs(args):
+    """The cut-offs of the requested risk-coverage sweep, or None without one."""
+    if args.s_cut_off_sweep is not None:
+        return [float(c) for c in args.s_cut_off_sweep]
+    if args.s_cut_off_steps is not None:
+        return np.linspace(0, 1, args.s_cut_off_steps + 1).tolist()
+    return None
 
 
 def load_test_set(args):
@@ -74,6 +99,9 @@ def evaluate(args):
 
     if args.input_type not in ('RGB', 'GH', 'H_RGB'):
         raise ValueError(f"input_type {args.input_type!r}: 'RGB', 'GH' or 'H_RGB' (utils/data_utils.py:223-226)")
+    cut_offs = sweep_cut_offs(args)
+    if cut_offs is not None and not args.selective:
+        raise ValueError("a selection cut-off sweep needs a selective network (--selective 1)")
     device = torch.device("cuda", args.local_rank[0])
     torch.cuda.set_device(device)
     dt = torch.bfloat16 if args.compute_dtype == 'bf16' else torch.float32
@@ -96,6 +124,8 @@ def evaluate(args):
                            input_type=args.input_type)
     ev = MT.SegMetrics(device, selective=bool(args.select_eval), rule="eval", cut_off=args.cut_off,
                        s_cut_off=args.s_cut_off, output_scale=args.single_scale)
+    sweep = None if cut_offs is None else MT.SelectiveSweep(device, cut_offs, rule="eval", cut_off=args.cut_off,
+                                                            output_scale=args.single_scale)
     print("Model Prediction...")
     with torch.no_grad():
         for x, target in loader:
@@ -119,7 +149,11 @@ def evaluate(args):
                 output = acc.div_(float(len(nets)))
             if args.select_eval and selection is None:
                 raise ValueError("--select_eval needs a selective network (--selective 1)")
-            ev.add_batch(output.contiguous(), target, None if selection is None else selection.contiguous())
+            output = output.contiguous()
+            selection = None if selection is None else selection.contiguous()
+            ev.add_batch(output, target, selection)
+            if sweep is not None:
+                sweep.add_batch(output, target, selection)
     cm = ev.confusion_matrix()
     selected, total = ev.selected_total()
     prec, rec = MT.precision(cm), MT.recall(cm)
@@ -142,13 +176,56 @@ def evaluate(args):
     os.makedirs(args.save_dir, exist_ok=True)
     with open(os.path.join(args.save_dir, "performance.json"), "w") as fh:
         json.dump(res, fh, indent=1)
+    if sweep is not None:
+        res = dict(res, risk_coverage=report_sweep(sweep.curve(), args.target_coverage, args.save_dir))
     return res
+
+
+CSV_COLUMNS = ("s_cut_off", "coverage", "rejection_ratio", "selected", "total", "risk", "Acc", "mIoU")
+
+
+def report_sweep(curve, target_coverage, save_dir):
+    """Print the risk-coverage table and write risk_coverage.json / risk_coverage.csv."""
+    from . import metrics as MT
+
+    doc = {"curve": curve}
+    print('    risk-coverage sweep of the selection cut-off:')
+    print('    ' + ' '.join(f'{c:>12}' for c in ("s_cut_off", "coverage", "risk", "mIoU")))
+    for r in curve:
+        print('    ' + ' '.join(f'{r[c]:12.6f}' for c in ("s_cut_off", "coverage", "risk", "mIoU")))
+    if target_coverage is not None:
+        cut = MT.cut_off_for_coverage(curve, target_coverage)
+        doc["target_coverage"] = target_coverage
+        doc["calibrated_s_cut_off"] = cut
+        doc["calibrated"] = None if cut is None else next(r for r in curve if r["s_cut_off"] == cut)
+        if cut is None:
+            doc["calibration_note"] = (f"coverage {target_coverage} is unreachable: the smallest cut-off "
+                                       f"{curve[0]['s_cut_off']} covers {curve[0]['coverage']}")
+            print(f'    target coverage {target_coverage}: unreachable (smallest cut-off '
+                  f'{curve[0]["s_cut_off"]} covers {curve[0]["coverage"]:.6f})')
+        else:
+            r = doc["calibrated"]
+            print(f'    target coverage {target_coverage}: s_cut_off {cut} (coverage {r["coverage"]:.6f}, '
+                  f'risk {r["risk"]:.6f}, mIoU {r["mIoU"]:.6f})')
+    os.makedirs(save_dir, exist_ok=True)
+    with open(os.path.join(save_dir, "risk_coverage.json"), "w") as fh:
+        json.dump(doc, fh, indent=1)
+    with open(os.path.join(save_dir, "risk_coverage.csv"), "w") as fh:
+        fh.write(",".join(CSV_COLUMNS + ("cm00", "cm01", "cm10", "cm11")) + "\n")
+        for r in curve:
+            cm = [int(v) for row in r["confusion_matrix"] for v in row]
+            fh.write(",".join([repr(r[c]) for c in CSV_COLUMNS] + [str(v) for v in cm]) + "\n")
+    return doc
 
 
 def main(argv=None):
     args = parse_arguments(sys.argv[1:] if argv is None else argv)
     print('')
-    print('args={}\n'.format(args))
+    shown = args
+    if sweep_cut_offs(args) is None:  # without a sweep the printed line is what it was before these flags
+        shown = argparse.Namespace(**{k: v for k, v in vars(args).items()
+                                      if k not in ('s_cut_off_sweep', 's_cut_off_steps', 'target_coverage')})
+    print('args={}\n'.format(shown))
     evaluate(args)
     return 0
 

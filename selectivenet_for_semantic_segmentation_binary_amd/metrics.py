@@ -12,10 +12,15 @@ masks are bit-exact by construction; e.g. t = 1.5612511e-16 for the training rul
 1.2318974e-07 for the eval rule at cut_off 0.5). The device then only
 compares and counts (`selunet_seg_metrics`): the 2x2 confusion matrix over selected pixels and
 the selected/total pixel counts, accumulated as uint64 across batches.
+
+`SelectiveSweep` does the same for a sorted list of selection cut-offs in one pass
+(`selunet_seg_metrics_sweep`): the risk-coverage curve, and `cut_off_for_coverage` to calibrate the
+cut-off to a wanted coverage.
 """
 from __future__ import annotations
 
 import functools
+import warnings
 
 import numpy as np
 import torch
@@ -143,3 +148,92 @@ def recall(cm):
 def dice(cm):
     with np.errstate(invalid="ignore", divide="ignore"):
         return 2 * np.diag(cm) / (np.sum(cm, axis=1) + np.sum(cm, axis=0))
+
+
+def sweep_thresholds(s_cut_offs, rule: str = "eval", output_scale: str = "sigmoid"):
+    """(cut-offs sorted and de-duplicated, their fp32 selection-logit thresholds). The reference's
+    rule is monotone in the cut-off, so the thresholds come out non-decreasing (checked): each pixel
+    then lies in exactly one bin between two of them. Pure host code."""
+    cuts = sorted({float(c) for c in s_cut_offs})
+    if not cuts:
+        raise ValueError("risk-coverage sweep: no cut-offs")
+    if any(np.isnan(c) for c in cuts):
+        raise ValueError("risk-coverage sweep: NaN cut-off")
+    if len(cuts) > K.SWEEP_MAX:
+        raise ValueError(f"risk-coverage sweep: {len(cuts)} distinct cut-offs, at most {K.SWEEP_MAX}")
+    thr = np.array([logit_threshold(rule, c, output_scale) for c in cuts], np.float32)
+    if np.any(thr[1:] < thr[:-1]):
+        raise ValueError(f"risk-coverage sweep: the logit thresholds of {cuts} are not non-decreasing: {thr}")
+    return cuts, thr
+
+
+class SelectiveSweep:
+    """Risk-coverage sweep of the selection cut-off in one pass over the data: per batch, one
+    `selunet_seg_metrics_sweep` call bins every pixel by how many of the sorted selection thresholds
+    its selection logit reaches and counts a 2x2 confusion matrix per bin. `sweep_curve` suffix-sums
+    the bins on the host into the counts `SegMetrics` would give at each cut-off alone (integer work:
+    bit-exact). The prediction rule (`cut_off`) is fixed, as in `SegMetrics`."""
+
+    def __init__(self, device, s_cut_offs, rule: str = "eval", cut_off: float = 0.5,
+                 output_scale: str = "sigmoid"):
+        self.s_cut_offs, thr = sweep_thresholds(s_cut_offs, rule, output_scale)
+        self.t_out = logit_threshold(rule, cut_off, output_scale)
+        self.thresholds = torch.tensor(thr, dtype=torch.float32, device=device)
+        self.bins = torch.zeros(len(self.s_cut_offs) + 1, 5, dtype=torch.int64, device=device)  # uint64 bits
+
+    def reset(self):
+        self.bins.zero_()
+
+    def add_batch(self, output: torch.Tensor, target: torch.Tensor, selection: torch.Tensor):
+        if selection is None:
+            raise ValueError("SelectiveSweep.add_batch needs the selection logits")
+        for name, t in (("output", output), ("target", target), ("selection", selection)):
+            if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
+                raise RuntimeError(f"SelectiveSweep.add_batch: {name} must be a contiguous cuda fp32 tensor")
+        if output.numel() != target.numel() or selection.numel() != output.numel():
+            raise ValueError("SelectiveSweep.add_batch: output, target and selection must have the same size")
+        K.call("selunet_seg_metrics_sweep", K.ptr(output), K.ptr(selection), K.ptr(target), output.numel(),
+               self.t_out, K.ptr(self.thresholds), len(self.s_cut_offs), K.ptr(self.bins), K.stream_ptr())
+
+    def raw(self) -> np.ndarray:
+        c = self.bins.clone()
+        parallel.allreduce_sums(c)
+        return c.cpu().numpy().astype(np.int64)
+
+    def curve(self) -> list:
+        return sweep_curve(self.raw(), self.s_cut_offs)
+
+
+def sweep_curve(bins, s_cut_offs) -> list:
+    """One row per cut-off (ascending) from the [(k+1), 5] bin counts of `SelectiveSweep.raw()`: a pixel
+    of bin b is selected at cut-off j exactly when b > j, so row j is the sum of the bins above j."""
+    bins = np.asarray(bins, np.int64)
+    cuts = [float(c) for c in s_cut_offs]
+    if bins.shape != (len(cuts) + 1, 5):
+        raise ValueError(f"sweep_curve: bins of shape {bins.shape} for {len(cuts)} cut-offs")
+    suffix = np.cumsum(bins[::-1], axis=0)[::-1]
+    total = int(bins[:, 4].sum())
+    rows = []
+    for j, c in enumerate(cuts):
+        cm = suffix[j + 1, :4].reshape(2, 2).astype(np.float64)
+        selected = int(suffix[j + 1, 4])
+        prec, rec = precision(cm), recall(cm)
+        with np.errstate(invalid="ignore", divide="ignore"), warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)  # nanmean of an all-NaN row: nothing selected
+            acc = float(pixel_accuracy(cm))
+            f1 = 2 * (prec * rec) / (prec + rec)
+            iou_class = np.diag(cm) / (cm.sum(1) + cm.sum(0) - np.diag(cm))
+            miou = float(mean_iou(cm))
+        rows.append({"s_cut_off": c, "confusion_matrix": cm.tolist(), "selected": selected, "total": total,
+                     "coverage": selected / total if total else float("nan"),
+                     "rejection_ratio": (total - selected) / max(total, 1),
+                     "Acc": acc, "risk": 1.0 - acc, "mIoU": miou, "IoU_class": iou_class.tolist(),
+                     "Prec": prec.tolist(), "Recall": rec.tolist(), "F1_Score": f1.tolist()})
+    return rows
+
+
+def cut_off_for_coverage(curve, target):
+    """The largest cut-off of the curve whose coverage is >= target (coverage does not increase with
+    the cut-off); None when even the smallest cut-off selects less."""
+    ok = [r["s_cut_off"] for r in curve if r["coverage"] >= target]
+    return max(ok) if ok else None
