@@ -2485,85 +2485,93 @@ bool conv3x3_wgrad_wino_eligible(const GatherArg& p, const GatherArg& q, int dty
   return option(SELUNET_OPT_WINO_WGRAD, 1) != 0 && dtype == SELUNET_F32 && conv3x3_wgrad_halo_eligible(p, q, dtype) && q.w % 2 == 0;
 }
 
-// splits of the Winograd weight gradient (64 x 64 tiles): ~256 workgroups over (co tile, ci chunk, split)
-static int wino_wgrad_tw() { return option(SELUNET_OPT_WINO_WGRAD_TW, 16) == 8 ? 8 : 16; }
+// Launch geometry shared by the three 3x3 weight gradients: (co tile, ci chunk) groups of bi x 64 columns, the
+// th x tw pixel tiles cut into `splits` runs of `per` tiles, one workgroup per (group, split).
+struct WgradGeom {
+  int bi, co_tiles, ci_chunks, tiles_x, tiles_y;
+  int64_t total, per, splits;
+  unsigned blocks;
+};
 
-int64_t conv3x3_wgrad_wino_splits(const GatherArg& p, const GatherArg& q, int64_t* per_out) {
-  const int co_tiles = p.K / 64, ci_chunks = q.Ctot / 64;
-  const int64_t total = (int64_t)q.n * cdiv(q.w, wino_wgrad_tw()) * cdiv(q.h, FTH);
-  const int64_t target = std::max<int64_t>(1, option(SELUNET_OPT_WGRAD_WGS, 256));
-  const int64_t want = std::max<int64_t>(1, cdiv(target, (int64_t)co_tiles * ci_chunks));
-  const int64_t per = cdiv(total, std::min(total, want));
-  if (per_out) *per_out = per;
-  return cdiv(total, per);
+static WgradGeom wgrad_geom(const GatherArg& p, const GatherArg& q, int bi, int th, int tw, int wgs_key) {
+  WgradGeom g;
+  g.bi = bi;
+  g.co_tiles = p.K / bi;
+  g.ci_chunks = q.Ctot / 64;
+  g.tiles_x = (int)cdiv(q.w, tw);
+  g.tiles_y = (int)cdiv(q.h, th);
+  g.total = (int64_t)q.n * g.tiles_x * g.tiles_y;
+  // workgroup target over (co tile, ci chunk, pixel split); each split adds ni*ld*4 bytes of
+  // partials for the fixed-order reduction to read. One workgroup per CU (256) measured best:
+  // 6.53 vs 6.94 ms/step at 16 images/GPU (512: two per CU, twice the partials), 11.8 vs 12.2 at
+  // 32, equal at 128; 128 and 384 lose (SELUNET_WGRAD_WGS, SELUNET_X2_WGRAD_WGS override)
+  const int64_t target = std::max<int64_t>(1, option(wgs_key, 256));
+  const int64_t want = std::max<int64_t>(1, cdiv(target, (int64_t)g.co_tiles * g.ci_chunks));
+  g.per = cdiv(g.total, std::min(g.total, want));
+  g.splits = cdiv(g.total, g.per);
+  g.blocks = (unsigned)(g.co_tiles * g.ci_chunks * g.splits);
+  return g;
 }
 
+static int wino_wgrad_tw() { return option(SELUNET_OPT_WINO_WGRAD_TW, 16) == 8 ? 8 : 16; }
+
+// the Winograd weight gradient: 64 x 64 column tiles
+static WgradGeom wgrad_wino_geom(const GatherArg& p, const GatherArg& q) {
+  return wgrad_geom(p, q, 64, FTH, wino_wgrad_tw(), SELUNET_OPT_WGRAD_WGS);
+}
+
+int64_t conv3x3_wgrad_wino_splits(const GatherArg& p, const GatherArg& q) { return wgrad_wino_geom(p, q).splits; }
+
 int conv3x3_wgrad_wino_launch(const GatherArg& p, const GatherArg& q, float* ws, int ldw, hipStream_t st) {
-  const int co_tiles = p.K / 64, ci_chunks = q.Ctot / 64;
+  const WgradGeom g = wgrad_wino_geom(p, q);
   const int tw = wino_wgrad_tw();
-  const int tiles_x = (int)cdiv(q.w, tw), tiles_y = (int)cdiv(q.h, FTH);
-  const int64_t total = (int64_t)q.n * tiles_x * tiles_y;
-  int64_t per;
-  const int64_t splits = conv3x3_wgrad_wino_splits(p, q, &per);
-  const unsigned blocks = (unsigned)(co_tiles * ci_chunks * splits);
   const int nw = option(SELUNET_OPT_WINO_WGRAD_WAVES, 12) == 8 ? 8 : 12;
   auto kern = tw == 8 ? (nw == 8 ? conv3x3_wgrad_wino_f32_kernel<8, 8> : conv3x3_wgrad_wino_f32_kernel<8, 12>)
                       : (nw == 8 ? conv3x3_wgrad_wino_f32_kernel<16, 8> : conv3x3_wgrad_wino_f32_kernel<16, 12>);
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(nw * 64), 0, st, p, q, co_tiles, ci_chunks, per, tiles_x, tiles_y,
-                     total, ws, (int64_t)p.K * ldw, ldw);
+  hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(nw * 64), 0, st, p, q, g.co_tiles, g.ci_chunks, g.per, g.tiles_x,
+                     g.tiles_y, g.total, ws, (int64_t)p.K * ldw, ldw);
   return check_launch("conv3x3_wgrad_wino");
 }
 
 // column tile of the split-fp16 weight gradient (plain and BN-fused forms alike; 64-column tiles for the fused
 // 128+-channel layers measured 4 % slower, profiles/r05g_wgrad_bn_bi64_ab.txt)
-int conv3x3_wgrad_x2_bi(const GatherArg& p, bool /*bn*/) { return p.K % 128 == 0 ? 128 : 64; }
+static int conv3x3_wgrad_x2_bi(const GatherArg& p) { return p.K % 128 == 0 ? 128 : 64; }
 
-// pixel-tile splits of the split-fp16 weight gradient: ~256 workgroups over (co tile, ci chunk, split)
-int64_t conv3x3_wgrad_x2_splits(const GatherArg& p, const GatherArg& q, int64_t* per_out, bool bn) {
-  const int bi = conv3x3_wgrad_x2_bi(p, bn);
-  const int co_tiles = p.K / bi, ci_chunks = q.Ctot / 64;
-  const int64_t total = (int64_t)q.n * cdiv(q.w, XTW) * cdiv(q.h, XTH);
-  const int64_t target = std::max<int64_t>(1, option(SELUNET_OPT_X2_WGRAD_WGS, 256));
-  const int64_t want = std::max<int64_t>(1, cdiv(target, (int64_t)co_tiles * ci_chunks));
-  const int64_t per = cdiv(total, std::min(total, want));
-  if (per_out) *per_out = per;
-  return cdiv(total, per);
+static WgradGeom wgrad_x2_geom(const GatherArg& p, const GatherArg& q) {
+  return wgrad_geom(p, q, conv3x3_wgrad_x2_bi(p), XTH, XTW, SELUNET_OPT_X2_WGRAD_WGS);
 }
+
+int64_t conv3x3_wgrad_x2_splits(const GatherArg& p, const GatherArg& q) { return wgrad_x2_geom(p, q).splits; }
 
 static unsigned* tq_counters(hipStream_t st);
 // SELUNET_OPT_TILE_QUEUE bit 1: the split-fp16 weight gradients take their pixel tiles from ticket counters
 static bool x2_wgrad_tile_queue() { return (option(SELUNET_OPT_TILE_QUEUE, 0) & 2) != 0; }
 
+// fused: the BN-fused form, kind its dA source (SELUNET_DA_*)
+template <bool TQ>
+static auto wgrad_x2_kernel(int bi, bool fused, int kind) {
+  return bi == 128 ? (fused ? conv3x3_wgrad_x2_kernel<128, 1, TQ> : conv3x3_wgrad_x2_kernel<128, 0, TQ>)
+         : kind == SELUNET_DA_POOL  ? conv3x3_wgrad_x2_kernel<64, 2, TQ>
+         : kind == SELUNET_DA_HEADS ? conv3x3_wgrad_x2_kernel<64, 3, TQ>
+         : (fused ? conv3x3_wgrad_x2_kernel<64, 1, TQ> : conv3x3_wgrad_x2_kernel<64, 0, TQ>);
+}
+
 int conv3x3_wgrad_x2_launch(const GatherArg& p, const GatherArg& q, float* ws, int ldo, const float* amax_p,
                             const float* amax_q0, const float* amax_q1, hipStream_t st, const WgradBnArg* bn) {
-  const int bi = conv3x3_wgrad_x2_bi(p, bn != nullptr);
-  const int co_tiles = p.K / bi, ci_chunks = q.Ctot / 64;
-  const int tiles_x = (int)cdiv(q.w, XTW), tiles_y = (int)cdiv(q.h, XTH);
-  const int64_t total = (int64_t)q.n * tiles_x * tiles_y;
-  int64_t per;
-  const int64_t splits = conv3x3_wgrad_x2_splits(p, q, &per, bn != nullptr);
-  const unsigned blocks = (unsigned)(co_tiles * ci_chunks * splits);
+  const WgradGeom g = wgrad_x2_geom(p, q);
   const int kind = bn ? bn->kind : -1;
-  SELUNET_REQUIRE(kind <= SELUNET_DA_TENSOR || bi == 64, "conv3x3_wgrad_x2: pool / heads dA sources need 64 columns");
+  SELUNET_REQUIRE(kind <= SELUNET_DA_TENSOR || g.bi == 64, "conv3x3_wgrad_x2: pool / heads dA sources need 64 columns");
+  unsigned* tq = nullptr;
   if (x2_wgrad_tile_queue()) {  // (co tile, ci chunk) groups take their pixel tiles from ticket counters
-    unsigned* tq = tq_counters(st);
-    if (tq == nullptr || co_tiles * ci_chunks > 64)
+    tq = tq_counters(st);
+    if (tq == nullptr || g.co_tiles * g.ci_chunks > 64)
       return fail(SELUNET_ELAUNCH, "conv3x3_wgrad_x2: tile-queue counters unavailable (set SELUNET_OPT_TILE_QUEUE "
                                    "before capturing the step) or more than 64 (co tile, ci chunk) groups");
-    auto k = bi == 128 ? (bn ? conv3x3_wgrad_x2_kernel<128, 1, true> : conv3x3_wgrad_x2_kernel<128, 0, true>)
-             : kind == SELUNET_DA_POOL  ? conv3x3_wgrad_x2_kernel<64, 2, true>
-             : kind == SELUNET_DA_HEADS ? conv3x3_wgrad_x2_kernel<64, 3, true>
-             : (bn ? conv3x3_wgrad_x2_kernel<64, 1, true> : conv3x3_wgrad_x2_kernel<64, 0, true>);
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(512), 0, st, p, q, ldo, co_tiles, ci_chunks, per, tiles_x, tiles_y,
-                       total, ws, (int64_t)p.K * ldo, amax_p, amax_q0, amax_q1, bn ? *bn : WgradBnArg{}, tq);
-    return check_launch("conv3x3_wgrad_x2");
   }
-  auto k = bi == 128 ? (bn ? conv3x3_wgrad_x2_kernel<128, 1> : conv3x3_wgrad_x2_kernel<128, 0>)
-           : kind == SELUNET_DA_POOL  ? conv3x3_wgrad_x2_kernel<64, 2>
-           : kind == SELUNET_DA_HEADS ? conv3x3_wgrad_x2_kernel<64, 3>
-           : (bn ? conv3x3_wgrad_x2_kernel<64, 1> : conv3x3_wgrad_x2_kernel<64, 0>);
-  hipLaunchKernelGGL(k, dim3(blocks), dim3(512), 0, st, p, q, ldo, co_tiles, ci_chunks, per, tiles_x, tiles_y, total,
-                     ws, (int64_t)p.K * ldo, amax_p, amax_q0, amax_q1, bn ? *bn : WgradBnArg{}, nullptr);
+  const bool fused = bn != nullptr;
+  auto k = tq ? wgrad_x2_kernel<true>(g.bi, fused, kind) : wgrad_x2_kernel<false>(g.bi, fused, kind);
+  hipLaunchKernelGGL(k, dim3(g.blocks), dim3(512), 0, st, p, q, ldo, g.co_tiles, g.ci_chunks, g.per, g.tiles_x,
+                     g.tiles_y, g.total, ws, (int64_t)p.K * ldo, amax_p, amax_q0, amax_q1, bn ? *bn : WgradBnArg{}, tq);
   return check_launch("conv3x3_wgrad_x2");
 }
 
@@ -2576,58 +2584,26 @@ bool conv3x3_wgrad_halo_eligible(const GatherArg& p, const GatherArg& q, int dty
   return true;
 }
 
-// pixel-tile splits of the halo weight gradient: ~512 workgroups over (co tile, ci chunk, split)
-static void wgrad_tile(int dtype, int& th, int& tw) {
-  th = dtype == SELUNET_F32 ? FTH : WTH;
-  tw = dtype == SELUNET_F32 ? FTW : WTW;
+// the halo weight gradient: 128-column tiles where the output channels allow, the dtype's pixel tile
+static WgradGeom wgrad_halo_geom(const GatherArg& p, const GatherArg& q, int dtype) {
+  const bool f32 = dtype == SELUNET_F32;
+  return wgrad_geom(p, q, p.K % 128 == 0 ? 128 : 64, f32 ? FTH : WTH, f32 ? FTW : WTW, SELUNET_OPT_WGRAD_WGS);
 }
 
-int64_t conv3x3_wgrad_halo_splits(const GatherArg& p, const GatherArg& q, int dtype, int64_t* per_out) {
-  const int ni = p.K;
-  const int bi = ni % 128 == 0 ? 128 : 64;
-  const int co_tiles = ni / bi, ci_chunks = q.Ctot / 64;
-  int th, tw;
-  wgrad_tile(dtype, th, tw);
-  const int64_t total = (int64_t)q.n * cdiv(q.w, tw) * cdiv(q.h, th);
-  // workgroup target over (co tile, ci chunk, pixel split); each split adds ni*ld*4 bytes of
-  // partials for the fixed-order reduction to read. One workgroup per CU (256) measured best:
-  // 6.53 vs 6.94 ms/step at 16 images/GPU (512: two per CU, twice the partials), 11.8 vs 12.2 at
-  // 32, equal at 128; 128 and 384 lose (SELUNET_WGRAD_WGS overrides)
-  const int64_t target = std::max<int64_t>(1, option(SELUNET_OPT_WGRAD_WGS, 256));
-  const int64_t want = std::max<int64_t>(1, cdiv(target, (int64_t)co_tiles * ci_chunks));
-  const int64_t per = cdiv(total, std::min(total, want));
-  if (per_out) *per_out = per;
-  return cdiv(total, per);
+int64_t conv3x3_wgrad_halo_splits(const GatherArg& p, const GatherArg& q, int dtype) {
+  return wgrad_halo_geom(p, q, dtype).splits;
 }
 
 // ws == nullptr: fp32 atomics into out (zeroed by the caller). Otherwise every split writes its
 // partial to ws[split][ni][ldo] (ws_stride = ni * ldo floats) and the caller reduces the splits.
 int conv3x3_wgrad_halo_launch(const GatherArg& p, const GatherArg& q, float* out, int ldo, float* ws, int dtype,
                               hipStream_t st) {
-  const int ni = p.K;
-  const int bi = ni % 128 == 0 ? 128 : 64;
-  const int co_tiles = ni / bi, ci_chunks = q.Ctot / 64;
-  int th, tw;
-  wgrad_tile(dtype, th, tw);
-  const int tiles_x = (int)cdiv(q.w, tw), tiles_y = (int)cdiv(q.h, th);
-  const int64_t total = (int64_t)q.n * tiles_x * tiles_y;
-  int64_t per;
-  const int64_t splits = conv3x3_wgrad_halo_splits(p, q, dtype, &per);
-  const unsigned blocks = (unsigned)(co_tiles * ci_chunks * splits);
-  const int64_t stride = (int64_t)ni * ldo;
-  if (dtype == SELUNET_F32) {
-    if (bi == 128)
-      hipLaunchKernelGGL((conv3x3_wgrad_halo_f32_kernel<128, 64>), dim3(blocks), dim3(512), 0, st, p, q, out, ldo,
-                         co_tiles, ci_chunks, per, tiles_x, tiles_y, total, ws, stride);
-    else
-      hipLaunchKernelGGL((conv3x3_wgrad_halo_f32_kernel<64, 32>), dim3(blocks), dim3(512), 0, st, p, q, out, ldo,
-                         co_tiles, ci_chunks, per, tiles_x, tiles_y, total, ws, stride);
-  } else if (bi == 128)
-    hipLaunchKernelGGL(conv3x3_wgrad_halo_kernel<128>, dim3(blocks), dim3(512), 0, st, p, q, out, ldo, co_tiles,
-                       ci_chunks, per, tiles_x, tiles_y, total, ws, stride);
-  else
-    hipLaunchKernelGGL(conv3x3_wgrad_halo_kernel<64>, dim3(blocks), dim3(512), 0, st, p, q, out, ldo, co_tiles,
-                       ci_chunks, per, tiles_x, tiles_y, total, ws, stride);
+  const WgradGeom g = wgrad_halo_geom(p, q, dtype);
+  const bool bi128 = g.bi == 128;
+  auto k = dtype == SELUNET_F32 ? (bi128 ? conv3x3_wgrad_halo_f32_kernel<128, 64> : conv3x3_wgrad_halo_f32_kernel<64, 32>)
+                                : (bi128 ? conv3x3_wgrad_halo_kernel<128> : conv3x3_wgrad_halo_kernel<64>);
+  hipLaunchKernelGGL(k, dim3(g.blocks), dim3(512), 0, st, p, q, out, ldo, g.co_tiles, g.ci_chunks, g.per, g.tiles_x,
+                     g.tiles_y, g.total, ws, (int64_t)p.K * ldo);
   return check_launch("conv3x3_wgrad_halo");
 }
 
@@ -2715,12 +2691,16 @@ static void launch_wino(const GatherArg& g, const float* u, int N, const EpiArg&
                      N, WINO_STEPS * g.Ctot, ep, n_tiles, tiles_x, tiles_y, (int)conv3x3_halo_tiles(g), gp);
 }
 
-bool conv3x3_wino_bn128(int N, const EpiArg& ep) {
-  return N % 128 == 0 && !(ep.mode == SELUNET_EP_SPLIT && ep.split % 128 != 0);
+// 128-column tiles whenever N allows, unless a SPLIT epilogue's boundary is no multiple of split_mult. The halo
+// and Winograd kernels write from registers and need the split on a tile boundary (128). The split-fp16 kernel's
+// LDS-staged epilogue routes each column to its SPLIT output itself, so a tile may straddle the split (8;
+// decoder_layer_1_2's data gradient, split at 64: one pass over its halo instead of two, 4.5 -> 3.x ms)
+bool conv3x3_bn128(int N, const EpiArg& ep, int split_mult) {
+  return N % 128 == 0 && !(ep.mode == SELUNET_EP_SPLIT && ep.split % split_mult != 0);
 }
 
 int conv3x3_wino_launch(const GatherArg& g, const float* u, int N, const EpiArg& ep, hipStream_t st) {
-  if (conv3x3_wino_bn128(N, ep)) launch_wino<128, 1>(g, u, N, ep, st);
+  if (conv3x3_bn128(N, ep, 128)) launch_wino<128, 1>(g, u, N, ep, st);
   else launch_wino<64, 2>(g, u, N, ep, st);
   return check_launch("conv3x3_wino");
 }
@@ -2789,36 +2769,27 @@ static int launch_x2(const GatherArg& g, const float* w, int N, const EpiArg& ep
   if (((int64_t)N * k_pad + N) * 4 >= (int64_t)1 << 31 || (int64_t)(HHT * g.w + HWT) * cmax * 4 >= (int64_t)1 << 31 ||
       (int64_t)3 * g.w + HWT >= 1 << 24 || (int64_t)cmax * 4 >= 1 << 24)
     return fail(SELUNET_EINVAL, "conv3x3_x2: operand too large for 32-bit staging offsets");
-  // 16x16x32 MFMAs at BN = 64 (1-4 % faster per layer); at BN = 128 they cost 20-25 % (the extra
-  // fragment registers spill: 180 B of scratch per lane against 44) — DESIGN.md §3
+  unsigned* tq = nullptr;
   if (x2_tile_queue()) {
-    unsigned* tq = tq_counters(st);
+    tq = tq_counters(st);
     if (tq == nullptr || n_tiles > 64)
       return fail(SELUNET_ELAUNCH, "conv3x3_x2: tile-queue counters unavailable (set SELUNET_OPT_TILE_QUEUE "
                                    "before capturing the step)");
-    hipLaunchKernelGGL((conv3x3_halo_persist_kernel<float, BN, true, BN == 64, true>), dim3((unsigned)(gp * n_tiles)),
-                       dim3(HTHREADS), 0, st, g, w, N, k_pad, ep, n_tiles, tiles_x, tiles_y,
-                       (int)conv3x3_halo_tiles(g), gp, w + (int64_t)N * k_pad, amax0, amax1, tq);
-    return 0;
   }
-  hipLaunchKernelGGL((conv3x3_halo_persist_kernel<float, BN, true, BN == 64>), dim3((unsigned)(gp * n_tiles)),
-                     dim3(HTHREADS), 0, st, g, w, N, k_pad, ep, n_tiles, tiles_x, tiles_y, (int)conv3x3_halo_tiles(g),
-                     gp, w + (int64_t)N * k_pad, amax0, amax1, nullptr);
+  // 16x16x32 MFMAs at BN = 64 (1-4 % faster per layer); at BN = 128 they cost 20-25 % (the extra
+  // fragment registers spill: 180 B of scratch per lane against 44) — DESIGN.md §3
+  auto k = tq ? conv3x3_halo_persist_kernel<float, BN, true, BN == 64, true>
+              : conv3x3_halo_persist_kernel<float, BN, true, BN == 64>;
+  hipLaunchKernelGGL(k, dim3((unsigned)(gp * n_tiles)), dim3(HTHREADS), 0, st, g, w, N, k_pad, ep, n_tiles, tiles_x,
+                     tiles_y, (int)conv3x3_halo_tiles(g), gp, w + (int64_t)N * k_pad, amax0, amax1, tq);
   return 0;
-}
-
-// 128-column tiles whenever N allows: unlike the Winograd kernel's register output transform, the
-// LDS-staged epilogue routes each column to its SPLIT output itself, so a tile may straddle the split
-// (decoder_layer_1_2's data gradient, split at 64: one pass over its halo instead of two, 4.5 -> 3.x ms)
-bool conv3x3_x2_bn128(int N, const EpiArg& ep) {
-  return N % 128 == 0 && !(ep.mode == SELUNET_EP_SPLIT && ep.split % 8 != 0);
 }
 
 int conv3x3_x2_launch(const GatherArg& g, const float* w, int N, const EpiArg& ep, const float* amax0,
                       const float* amax1, hipStream_t st) {
   if (conv3x3_x2d_eligible(g, N)) return conv3x3_x2d_launch(g, w, ep, amax0, amax1, st);  // 64 columns
   if (conv3x3_x2p_eligible(g, N)) return conv3x3_x2p_launch(g, w, N, ep, amax0, amax1, st);  // 128, two per CU
-  if (int rc = conv3x3_x2_bn128(N, ep) ? launch_x2<128>(g, w, N, ep, amax0, amax1, st)
+  if (int rc = conv3x3_bn128(N, ep, 8) ? launch_x2<128>(g, w, N, ep, amax0, amax1, st)
                                        : launch_x2<64>(g, w, N, ep, amax0, amax1, st))
     return rc;
   return check_launch("conv3x3_x2");
@@ -2828,7 +2799,7 @@ int conv3x3_halo_launch(const GatherArg& g, const void* b, int N, int k_pad, con
                         hipStream_t st) {
   // single-chunk layers use 64-column tiles: LDS for two workgroups per CU
   const bool one = halo_one_chunk(g, dtype);
-  const bool bn128 = !one && N % 128 == 0 && !(ep.mode == SELUNET_EP_SPLIT && ep.split % 128 != 0);
+  const bool bn128 = !one && conv3x3_bn128(N, ep, 128);
   if (dtype == SELUNET_F32) {
     if (bn128) launch_halo<float, 128>(g, b, N, k_pad, ep, st);
     else launch_halo<float, 64>(g, b, N, k_pad, ep, st);

@@ -1146,7 +1146,7 @@ extern "C" const char* selunet_conv3x3_wino_kernel_name(int32_t n_cols, int32_t 
   EpiArg e{};
   e.mode = mode;
   e.split = split;
-  return conv3x3_wino_bn128(n_cols, e) ? "conv3x3_wino<f32,128>" : "conv3x3_wino<f32,64>";
+  return conv3x3_bn128(n_cols, e, 128) ? "conv3x3_wino<f32,128>" : "conv3x3_wino<f32,64>";
 }
 
 extern "C" int selunet_conv3x3_wino(const selunet_gather* a, const float* u, int32_t n_cols,
@@ -1236,7 +1236,7 @@ extern "C" const char* selunet_conv3x3_x2_kernel_name(const selunet_gather* a, i
   if (make_gather(a, SELUNET_F32, g, 4)) return "?";
   if (conv3x3_x2d_eligible(g, n_cols)) return "conv3x3_x2d<f32,64>";
   if (conv3x3_x2p_eligible(g, n_cols)) return "conv3x3_x2p<f32,128>";
-  return conv3x3_x2_bn128(n_cols, e) ? "conv3x3_x2<f32,128>" : "conv3x3_x2<f32,64>";
+  return conv3x3_bn128(n_cols, e, 8) ? "conv3x3_x2<f32,128>" : "conv3x3_x2<f32,64>";
 }
 
 extern "C" int64_t selunet_conv3x3_x2_stats_rows(const selunet_gather* a, int32_t n_cols) {
@@ -1388,9 +1388,9 @@ static int plan_wgrad(const selunet_gather* p, const selunet_gather* q, int32_t 
   w.halo = halo_enabled() && conv3x3_wgrad_halo_eligible(w.gp, w.gq, dtype);
   w.wino = w.halo && conv3x3_wgrad_wino_eligible(w.gp, w.gq, dtype);
   if (w.wino) {
-    w.splits = conv3x3_wgrad_wino_splits(w.gp, w.gq, nullptr);
+    w.splits = conv3x3_wgrad_wino_splits(w.gp, w.gq);
   } else if (w.halo) {
-    w.splits = conv3x3_wgrad_halo_splits(w.gp, w.gq, dtype, nullptr);
+    w.splits = conv3x3_wgrad_halo_splits(w.gp, w.gq, dtype);
   } else {
     // bf16, vector operands, 256-column tiles possible (the ConvTranspose2d weight gradients): 256 x 256 or
     // 128 x 256 tiles, pixel splits sized for 256 workgroups (gemm_wgrad_x2's tiling)
@@ -1546,19 +1546,19 @@ extern "C" int selunet_gemm_wgrad_ws_to(const selunet_gather* p, const selunet_g
 
 // fp32 3x3 weight gradient on split-fp16 operands (conv3x3_wgrad_x2_kernel + the fixed-order split
 // reduction into the Conv2d layout)
-static int plan_wgrad_x2(const selunet_gather* p, const selunet_gather* q, WgradPlan& w, bool bn = false) {
+static int plan_wgrad_x2(const selunet_gather* p, const selunet_gather* q, WgradPlan& w) {
   if (int rc = plan_wgrad(p, q, SELUNET_F32, w)) return rc;
   SELUNET_REQUIRE(halo_enabled() && conv3x3_wgrad_halo_eligible(w.gp, w.gq, SELUNET_F32) && w.gq.K % 9 == 0,
                   "conv3x3_wgrad_x2: operands not eligible (P: 1 tap, K %% 64 == 0; Q: 3x3, channels %% 64 == 0, "
                   "h >= 8, w >= 16)");
-  w.splits = conv3x3_wgrad_x2_splits(w.gp, w.gq, nullptr, bn);
+  w.splits = conv3x3_wgrad_x2_splits(w.gp, w.gq);
   return 0;
 }
 
 extern "C" int64_t selunet_conv3x3_wgrad_x2_ws_bytes(const selunet_gather* p, const selunet_gather* q) {
-  WgradPlan w, wb;  // (the plain and the BN-fused forms' split plans)
-  if (plan_wgrad_x2(p, q, w) || plan_wgrad_x2(p, q, wb, true)) return -1;
-  return std::max(w.splits, wb.splits) * (int64_t)w.ni * w.nj_pad * 4;
+  WgradPlan w;  // (the plain and the BN-fused forms share one split plan)
+  if (plan_wgrad_x2(p, q, w)) return -1;
+  return w.splits * (int64_t)w.ni * w.nj_pad * 4;
 }
 
 extern "C" int selunet_conv3x3_wgrad_x2(const selunet_gather* p, const selunet_gather* q, float* ws, int64_t ws_bytes,
@@ -1585,7 +1585,7 @@ extern "C" int selunet_conv3x3_wgrad_x2_bn_src(const selunet_gather* p, const se
                                                const float* amax_q1, const selunet_bn_bwd_stats* bnb, const float* coef,
                                                const selunet_da_source* src, float* dy, float* dy_amax, void* stream) {
   WgradPlan w;
-  if (int rc = plan_wgrad_x2(p, q, w, true)) return rc;
+  if (int rc = plan_wgrad_x2(p, q, w)) return rc;
   const int64_t need = w.splits * (int64_t)w.ni * w.nj_pad * 4;
   SELUNET_REQUIRE(out != nullptr && ws != nullptr && ws_bytes >= need, "conv3x3_wgrad_x2_bn: out / workspace of %lld bytes",
                   (long long)need);

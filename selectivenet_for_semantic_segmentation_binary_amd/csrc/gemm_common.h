@@ -451,11 +451,10 @@ int conv3x3_halo_launch(const GatherArg& g, const void* b, int N, int k_pad, con
 // fp32 1-D Winograd F(2,3) forward / data gradient (conv3x3.hip, selunet_conv3x3_wino)
 bool conv3x3_wino_shape_ok(int h, int w, int c_in, int c_src0, int n_cols);
 bool conv3x3_wgrad_wino_eligible(const GatherArg& p, const GatherArg& q, int dtype);
-int64_t conv3x3_wgrad_wino_splits(const GatherArg& p, const GatherArg& q, int64_t* per_out);
+int64_t conv3x3_wgrad_wino_splits(const GatherArg& p, const GatherArg& q);
 int conv3x3_wgrad_wino_launch(const GatherArg& p, const GatherArg& q, float* ws, int ldw, hipStream_t st);
 bool conv3x3_wino_eligible(const GatherArg& g, int N);
-bool conv3x3_wino_bn128(int N, const EpiArg& ep);
-bool conv3x3_x2_bn128(int N, const EpiArg& ep);
+bool conv3x3_bn128(int N, const EpiArg& ep, int split_mult);  // 128-column tiles (split_mult: 128, split-fp16 8)
 int conv3x3_wino_launch(const GatherArg& g, const float* u, int N, const EpiArg& ep, hipStream_t st);
 // fp32 forward / data gradient on split-fp16 operands (conv3x3.hip, selunet_conv3x3_x2)
 bool conv3x3_x2_shape_ok(int h, int w, int c_in, int c_src0, int n_cols);
@@ -494,8 +493,7 @@ int64_t conv3x3_x2d_rows(const GatherArg& g);
 int conv3x3_x2d_launch(const GatherArg& g, const float* w, const EpiArg& ep, const float* amax0, const float* amax1,
                        hipStream_t st);
 bool conv3x3_wgrad_halo_eligible(const GatherArg& p, const GatherArg& q, int dtype);
-int64_t conv3x3_wgrad_x2_splits(const GatherArg& p, const GatherArg& q, int64_t* per_out, bool bn = false);
-int conv3x3_wgrad_x2_bi(const GatherArg& p, bool bn);
+int64_t conv3x3_wgrad_x2_splits(const GatherArg& p, const GatherArg& q);
 // SELUNET_OPT_TILE_QUEUE and the split-fp16 persistent kernel's statistics slab rows (conv3x3.hip)
 bool x2_tile_queue();
 // the 128-column split-fp16 3x3 kernel with two 256-thread workgroups per CU (conv3x3_x2p.hip)
@@ -528,7 +526,7 @@ int conv3x3_wgrad_x2_launch(const GatherArg& p, const GatherArg& q, float* ws, i
                             const WgradBnArg* bn = nullptr);
 int conv3x3_wgrad_halo_launch(const GatherArg& p, const GatherArg& q, float* out, int ldo, float* ws, int dtype,
                               hipStream_t st);
-int64_t conv3x3_wgrad_halo_splits(const GatherArg& p, const GatherArg& q, int dtype, int64_t* per_out);
+int64_t conv3x3_wgrad_halo_splits(const GatherArg& p, const GatherArg& q, int dtype);
 bool halo_enabled();
 
 }  // namespace selunet

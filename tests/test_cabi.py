@@ -106,6 +106,133 @@ def test_host_queries_need_no_device(lib):
         K.set_option("X2D", prev)
 
 
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def _splits(total, groups, target=256):
+    """The pixel-tile split plan of the 3x3 weight gradients, restated: about `target` workgroups over
+    (co tile, ci chunk, split), every split taking the same `per` pixel tiles."""
+    want = max(1, _cdiv(max(1, target), groups))
+    per = _cdiv(total, min(total, want))
+    return _cdiv(total, per)
+
+
+class _options:
+    """Set options by name for a block (value -1: the default) and put the previous values back."""
+
+    def __init__(self, **kv):
+        self.kv = kv
+
+    def __enter__(self):
+        self.prev = [(k, K.set_option(k, v)) for k, v in self.kv.items()]
+
+    def __exit__(self, *exc):
+        for k, v in reversed(self.prev):
+            K.set_option(k, v)
+
+
+# (n, h, w, co, Q source channels); the fourth has fewer pixel tiles than the plan wants splits
+WGRAD_SHAPES = [(16, 256, 256, 64, (64,)), (16, 128, 128, 128, (128,)), (2, 16, 24, 256, (128,)),
+                (1, 8, 16, 64, (64,)), (128, 32, 32, 512, (512,)), (2, 16, 24, 128, (64, 64))]
+
+
+def test_wgrad_split_plans_without_a_device(lib):
+    """The host-side planning of the 3x3 weight gradients, pinned against a restatement: the workspace
+    queries give splits * ni * row * 4 bytes with the split plan above, per path (its column tile, pixel
+    tile, row length and workgroup-target option)."""
+    import torch
+    K.load()
+    fake = torch.empty(64, dtype=torch.float32)  # never dereferenced
+
+    def operands(n, h, w, co, cis):
+        gp = K.gather(n, h, w, 1, K.source(fake, co))
+        gq = K.gather(n, h, w, 9, *[K.source(fake, c) for c in cis])
+        return ctypes.byref(gp), ctypes.byref(gq), (gp, gq)
+
+    def tiles(n, h, w, th, tw):
+        return n * _cdiv(h, th) * _cdiv(w, tw)
+
+    def bi(co):
+        return 128 if co % 128 == 0 else 64
+
+    base = dict(HALO=-1, WGRAD_WGS=-1, X2_WGRAD_WGS=-1, WINO_WGRAD=-1, WINO_WGRAD_TW=-1)
+    x2_splits = []
+    with _options(**base):
+        for n, h, w, co, cis in WGRAD_SHAPES:
+            ci = sum(cis)
+            p, q, _keep = operands(n, h, w, co, cis)
+            ld = K.query("selunet_wgrad_ld", 9 * ci)
+            groups = (co // bi(co)) * (ci // 64)
+            # split-fp16: 128- or 64-column tiles of 8x8 pixels, partial rows of ld floats
+            s = _splits(tiles(n, h, w, 8, 8), groups)
+            x2_splits.append(s)
+            assert K.query("selunet_conv3x3_wgrad_x2_ws_bytes", p, q) == s * co * ld * 4, (n, h, w, co, cis)
+            # fp32 Winograd: 64-column tiles of 8x16 pixels, partial rows of the 12 planes
+            s = _splits(tiles(n, h, w, 8, 16), (co // 64) * (ci // 64))
+            assert K.query("selunet_gemm_wgrad_ws_bytes", p, q, K.F32) == s * co * 12 * ci * 4, (n, h, w, co, cis)
+            # fp32 halo: 8x8 pixels; bf16 halo: 8x16 pixels
+            with _options(WINO_WGRAD=0):
+                s = _splits(tiles(n, h, w, 8, 8), groups)
+                assert K.query("selunet_gemm_wgrad_ws_bytes", p, q, K.F32) == s * co * ld * 4, (n, h, w, co, cis)
+            s = _splits(tiles(n, h, w, 8, 16), groups)
+            assert K.query("selunet_gemm_wgrad_ws_bytes", p, q, K.BF16) == s * co * ld * 4, (n, h, w, co, cis)
+        assert x2_splits[:5] == [256, 128, 12, 2, 8]
+        # each path follows its own workgroup-target option
+        n, h, w, co, cis = WGRAD_SHAPES[1]
+        p, q, _keep = operands(n, h, w, co, cis)
+        ld = K.query("selunet_wgrad_ld", 9 * 128)
+        want_x2 = {t: _splits(tiles(n, h, w, 8, 8), 2, t) * co * ld * 4 for t in (64, 256)}
+        want_bf = {t: _splits(tiles(n, h, w, 8, 16), 2, t) * co * ld * 4 for t in (64, 256)}
+        want_wi = {t: _splits(tiles(n, h, w, 8, 16), 4, t) * co * 12 * 128 * 4 for t in (64, 256)}
+        assert want_x2[64] != want_x2[256] and want_bf[64] != want_bf[256]
+        with _options(X2_WGRAD_WGS=64):
+            assert K.query("selunet_conv3x3_wgrad_x2_ws_bytes", p, q) == want_x2[64]
+            assert K.query("selunet_gemm_wgrad_ws_bytes", p, q, K.BF16) == want_bf[256]
+        with _options(WGRAD_WGS=64):
+            assert K.query("selunet_conv3x3_wgrad_x2_ws_bytes", p, q) == want_x2[256]
+            assert K.query("selunet_gemm_wgrad_ws_bytes", p, q, K.BF16) == want_bf[64]
+            assert K.query("selunet_gemm_wgrad_ws_bytes", p, q, K.F32) == want_wi[64]
+        assert K.query("selunet_conv3x3_wgrad_x2_ws_bytes", p, q) == want_x2[256]
+        assert K.query("selunet_gemm_wgrad_ws_bytes", p, q, K.BF16) == want_bf[256]
+
+
+def test_x2_forward_geometry_without_a_device(lib):
+    """The split-fp16 3x3 forward on 128-column tiles: kernel name, the tile-width predicate under a SPLIT
+    epilogue (beside the Winograd kernel's), and the statistics rows of either tile schedule."""
+    import torch
+    fake = torch.empty(64, dtype=torch.float32)  # never dereferenced
+    name = lambda g, nc, mode=K.EP_PLAIN, split=0: K.query(  # noqa: E731
+        "selunet_conv3x3_x2_kernel_name", ctypes.byref(g), nc, mode, split)
+    rows = lambda g, nc: K.query("selunet_conv3x3_x2_stats_rows", ctypes.byref(g), nc)  # noqa: E731
+    wino = lambda nc, mode, split: K.query("selunet_conv3x3_wino_kernel_name", nc, mode, split)  # noqa: E731
+    big = K.gather(16, 128, 128, 9, K.source(fake, 128))   # 1024 pixel tiles of 16x16
+    odd = K.gather(2, 20, 24, 9, K.source(fake, 128))      # 8 pixel tiles
+    wgs = K.query("selunet_set_halo_workgroups", 256)
+    try:
+        with _options(HALO=-1, HALO_PERSIST=-1, X2D=-1, TILE_QUEUE=0):
+            for nc in (128, 256, 512):
+                assert name(big, nc) == b"conv3x3_x2<f32,128>"
+                assert rows(big, nc) == min(1024, 256 // (nc // 128))
+                assert rows(odd, nc) == min(8, 256 // (nc // 128))
+            assert name(big, 192) == b"conv3x3_x2<f32,64>" and rows(big, 192) == 256
+            # a SPLIT epilogue keeps 128 columns at any split the LDS-staged epilogue can route (a multiple
+            # of 8); the Winograd kernel's register epilogue needs the split on a tile boundary
+            assert name(big, 128, K.EP_SPLIT, 64) == b"conv3x3_x2<f32,128>"
+            assert name(big, 128, K.EP_SPLIT, 68) == b"conv3x3_x2<f32,64>"
+            assert wino(256, K.EP_SPLIT, 128) == b"conv3x3_wino<f32,128>"
+            assert wino(128, K.EP_SPLIT, 64) == b"conv3x3_wino<f32,64>"
+            assert wino(128, K.EP_PLAIN, 0) == b"conv3x3_wino<f32,128>"
+            assert wino(192, K.EP_PLAIN, 0) == b"conv3x3_wino<f32,64>"
+            # the ticket-counter schedule flushes statistics per pixel tile; its counters live on a device,
+            # so without one the option is refused and only the static half above is checked
+            if K.set_option("TILE_QUEUE", 1) >= 0:
+                assert name(big, 256) == b"conv3x3_x2<f32,128>"
+                assert rows(big, 256) == 1024 and rows(odd, 256) == 8
+    finally:
+        K.query("selunet_set_halo_workgroups", wgs)
+
+
 def test_invalid_arguments_fail_with_a_message(lib):
     h = K.load()
     # unsupported channel count for the BN reduction: rejected on the host before any launch
