@@ -694,6 +694,33 @@ int selunet_seg_metrics_sweep(const float* out, const float* sel, const float* t
                               float t_out, const float* t_sel, int32_t k,
                               unsigned long long* bins, void* stream);
 
+/* Per-patch report (the reference's get_performance, utils/compute_metric.py:93-148, per image of a
+ * batch of n images of hw pixels each; out / sel / target [n][hw] fp32, sel nullable).
+ * Both calls: EINVAL for a null pointer (sel may be null), n < 1, hw < 1, hw % 4 != 0 or hw > 2^20
+ * (the 32-bit on-chip partial counts are sized for it), out / sel / target not 16-B aligned, rows
+ * not 8-B aligned. Integer atomics only: the result does not depend on scheduling. */
+/* Row i (i < n) += the six counts of selunet_seg_metrics over image i alone
+ * (pixels [i*hw, (i+1)*hw)): rows [n][6], uint64, caller-zeroed. */
+int selunet_seg_metrics_rows(const float* out, const float* sel, const float* target,
+                             int32_t n, int64_t hw, float t_out, float t_sel,
+                             unsigned long long* rows, void* stream);
+/* Exact per-image Mann-Whitney statistic of the prediction logit.
+ * rows [n][4] uint64, caller-zeroed, += {two_u, n_pos, n_neg, n_nan}.
+ * A pixel is considered when label = (int)(uint8_t)target < 2 (the rule of selunet_seg_metrics), it
+ * is selected (sel == NULL or sel >= t_sel) and out is not NaN; considered pixels of label 1 form P,
+ * of label 0 form N; selected pixels of label < 2 with a NaN out are counted in n_nan only.
+ *   two_u = sum over p in P of ( 2 * #{q in N: out_q < out_p} + #{q in N: out_q == out_p} ),
+ *   n_pos = |P|, n_neg = |N|,
+ * in the numeric fp32 order (-0 == +0; +-inf and denormals are ordinary values). The ROC AUC of the
+ * image, ties at one half (sklearn's roc_auc_score), is two_u / (2 * n_pos * n_neg).
+ * The statistic is taken on the logit, not on its sigmoid: the fp32 sigmoid is monotone but merges
+ * neighbouring and saturated logits into ties, so the logit is the finer ranking.
+ * No workspace: the negatives are sorted on chip in chunks of SELUNET_AUC_CHUNK pixels. */
+#define SELUNET_AUC_CHUNK 4096
+int selunet_patch_auc(const float* out, const float* sel, const float* target,
+                      int32_t n, int64_t hw, float t_sel,
+                      unsigned long long* rows, void* stream);
+
 /* ---- multi-GPU overlap probe (bench/tools only, not on the training path) ------
  * Stand-in for one bucketed RCCL all-reduce kernel on a single GPU: n_wg workgroups of 256 threads
  * reduce-copy dst[i] += src[i] over their slices of [0, n) (n % 4 == 0, 16-B aligned), repeatedly,

@@ -10,12 +10,14 @@ Drop-in replacements for the reference's hot path (yellofi/SelectiveNet_for_sema
 * `CrossEntropyLoss`                    <- torch.nn.CrossEntropyLoss (train.py:80)
 * `Adam`                                <- torch.optim.Adam (train.py:90)
 * `SelectiveSweep`                       risk-coverage sweep of eval.py's --s_cut_off in one pass
-* `parallel.init_data_parallel`         <- torch.nn.DataParallel (train.py:131-134)
+* `PatchReport`                          per-patch counts, get_performance metrics and exact ROC AUC
+                                        <- utils/compute_metric.py:93-148 (unused there)
+* `parallel.init_data_parallel`        <- torch.nn.DataParallel (train.py:131-134)
 
 All compute runs in libselunet.so (HIP, gfx950); there is no CPU fallback.
 """
 from .layout import count_params, state_dict_keys  # noqa: F401
-from .metrics import SelectiveSweep  # noqa: F401
+from .metrics import PatchReport, SelectiveSweep  # noqa: F401
 from .model import CBR_2D, UNet, UNet_B  # noqa: F401
 from .optim import Adam  # noqa: F401
 from .selective_loss import (BCEWithLogitsLoss, CrossEntropyLoss, calc_selective_risk_image,  # noqa: F401

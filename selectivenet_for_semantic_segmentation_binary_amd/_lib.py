@@ -23,6 +23,7 @@ DA_TENSOR, DA_POOL, DA_HEADS = 0, 1, 2  # selunet_da_source kinds
 GEMM_BM = 128
 ADAM_CHUNK = 4096
 SWEEP_MAX = 256  # SELUNET_SWEEP_MAX
+AUC_CHUNK = 4096  # SELUNET_AUC_CHUNK
 
 
 class Source(ctypes.Structure):
@@ -195,6 +196,8 @@ SIGNATURES = {
     "selunet_prep_batch_mode": (c_int32, [P, P, P, c_int32, c_int32, c_int32, c_int32, P, P, P]),
     "selunet_seg_metrics": (c_int32, [P, P, P, c_int64, c_float, c_float, P, P]),
     "selunet_seg_metrics_sweep": (c_int32, [P, P, P, c_int64, c_float, P, c_int32, P, P]),
+    "selunet_seg_metrics_rows": (c_int32, [P, P, P, c_int32, c_int64, c_float, c_float, P, P]),
+    "selunet_patch_auc": (c_int32, [P, P, P, c_int32, c_int64, c_float, P, P]),
     "selunet_set_option": (c_int64, [c_int32, c_int64]),
     "selunet_cu_hold": (c_int32, [P, P, c_int64, c_int32, c_float, P]),
 }

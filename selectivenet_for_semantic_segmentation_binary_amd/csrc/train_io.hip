@@ -11,6 +11,9 @@
 //    device, so the loop never copies the [N,H,W] outputs to the host.
 //  * selunet_seg_metrics_sweep: the same counts at up to 256 selection cut-offs in one pass (the
 //    risk-coverage curve), as a per-bin histogram the host suffix-sums.
+//  * selunet_seg_metrics_rows / selunet_patch_auc: the per-patch report (the reference's unused
+//    get_performance, utils/compute_metric.py:93-148): selunet_seg_metrics' counts per image, and the
+//    exact integer Mann-Whitney statistic behind each image's ROC AUC.
 //
 // All are byte/int work (no MFMA) in one pass over the data with 16-B coalesced loads; at an eval
 // batch the metrics kernels are bound by their launch and their closing atomics, not by HBM.
@@ -107,9 +110,10 @@ __global__ void prep_batch_kernel(const uint8_t* __restrict__ img, const uint8_t
 // A pixel is counted iff 0 <= label < 2 and (no selection head or sel >= t_sel).
 // pred = out >= t_out: t_out / t_sel are the smallest fp32 logits the reference's host rule maps
 // to 1 (computed once on the host from the same numpy expression, see metrics.py).
-__global__ void seg_metrics_kernel(const float* __restrict__ out, const float* __restrict__ sel,
-                                   const float* __restrict__ target, int64_t p, float t_out, float t_sel,
-                                   unsigned long long* __restrict__ counts) {
+// The workgroups blockIdx.x of gridDim.x share the p pixels; a grid's y dimension is the caller's.
+__device__ __forceinline__ void seg_metrics_block(const float* __restrict__ out, const float* __restrict__ sel,
+                                                  const float* __restrict__ target, int64_t p, float t_out,
+                                                  float t_sel, unsigned long long* __restrict__ counts) {
   unsigned c[5] = {0, 0, 0, 0, 0};
   const int64_t p4 = p >> 2;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -145,6 +149,210 @@ __global__ void seg_metrics_kernel(const float* __restrict__ out, const float* _
     atomicAdd(counts + threadIdx.x, s);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(counts + 5, (unsigned long long)p);
+}
+
+__global__ void seg_metrics_kernel(const float* __restrict__ out, const float* __restrict__ sel,
+                                   const float* __restrict__ target, int64_t p, float t_out, float t_sel,
+                                   unsigned long long* __restrict__ counts) {
+  seg_metrics_block(out, sel, target, p, t_out, t_sel, counts);
+}
+
+// The same counts per image: blockIdx.y is the image, its hw pixels shared by the gridDim.x workgroups
+// of the row. A thread counts at most hw <= 2^20 pixels into its 32-bit counters.
+__global__ void seg_metrics_rows_kernel(const float* __restrict__ out, const float* __restrict__ sel,
+                                        const float* __restrict__ target, int64_t hw, float t_out, float t_sel,
+                                        unsigned long long* __restrict__ rows) {
+  const int64_t base = (int64_t)blockIdx.y * hw;
+  seg_metrics_block(out + base, sel ? sel + base : nullptr, target + base, hw, t_out, t_sel, rows + blockIdx.y * 6);
+}
+
+// Exact per-image Mann-Whitney statistic of the prediction logit (the integer form of a ROC AUC with
+// ties at one half). With P / N the considered pixels of label 1 / 0 (considered: label < 2, selected,
+// logit not NaN),
+//   two_u = sum over p in P of ( #{q in N: out_q < out_p} + #{q in N: out_q <= out_p} ),
+// and AUC = two_u / (2 |P| |N|). fp32 values map to 32-bit keys whose unsigned order is the numeric
+// order (-0 folded into +0 first; the sign bit flipped for v >= 0, every bit for v < 0), so "less" and
+// "less or equal" are both lower bounds in a sorted key list: #{k <= x} = #{k < x + 1}.
+//
+// Workgroup (c, i) sorts the keys of the considered negatives of chunk c of image i in LDS (every other
+// slot holds the sentinel 0xFFFFFFFF, which no considered value maps to: NaNs are left out and +inf is
+// 0xFF800000; sentinels sort last and are below no search key), then streams all hw pixels of the
+// image and, for each considered positive, adds the two lower bounds of its key in the chunk. Summed
+// over the chunks of the image that is the statistic. Workgroup (0, i) also counts |P|, |N| and the NaN
+// logits. Integer adds only, so the result does not depend on scheduling.
+//
+// 32-bit partial counts at the largest hw = 2^20: a thread streams hw / AUC_TPB = 2^10 pixels, each adds
+// at most 2 * SELUNET_AUC_CHUNK = 2^13, so a thread's sum is <= 2^23 and a wave's (64 threads) <= 2^29;
+// the class counts are <= 2^10 per thread. Waves are summed in 64 bits; two_u itself is at most
+// 2 * (hw/2)^2 = 2^39 per image and call.
+//
+// 1024 threads: the searches are chains of dependent LDS reads, and sixteen waves per CU hide their
+// latency where four did not (16 x 256 x 256 pixels: 168 us with 256 threads).
+constexpr int64_t PATCH_MAX_HW = (int64_t)1 << 20;  // pixels per image the per-image calls take
+constexpr int32_t PATCH_GRID_Y = 32768;             // images per launch (blockIdx.y)
+constexpr int AUC_CHUNK = SELUNET_AUC_CHUNK;
+constexpr int AUC_TPB = 1024;
+constexpr unsigned AUC_SENTINEL = 0xFFFFFFFFu;
+static_assert((AUC_CHUNK & (AUC_CHUNK - 1)) == 0 && AUC_CHUNK % (AUC_TPB * 4) == 0 && AUC_CHUNK <= 4096,
+              "AUC chunk: a power of two, whole 16-B loads per thread, 2^23 per thread at hw = 2^20");
+
+__device__ __forceinline__ unsigned auc_key(float v) {
+  unsigned b = __float_as_uint(v);
+  b = b == 0x80000000u ? 0u : b;  // -0 == +0
+  return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+
+__global__ __launch_bounds__(AUC_TPB) void patch_auc_kernel(const float* __restrict__ out,
+                                                            const float* __restrict__ sel,
+                                                            const float* __restrict__ target, int64_t hw,
+                                                            float t_sel, unsigned long long* __restrict__ rows) {
+  __shared__ unsigned keys[AUC_CHUNK];
+  __shared__ unsigned red[AUC_TPB / 64][4];
+  const int64_t base = (int64_t)blockIdx.y * hw;
+  out += base;
+  target += base;
+  if (sel) sel += base;
+  const int tid = threadIdx.x;
+  // label.astype('uint8') < 2 and selected, as seg_metrics_kernel; NaN logits are told apart by the caller
+  auto label_of = [&](float s, float t) {
+    const int lab = (int)(uint8_t)t;
+    return (sel == nullptr || s >= t_sel) && lab < 2 ? lab : 2;
+  };
+
+  // ---- this chunk's considered negatives as keys, everything else (and the ragged tail) the sentinel
+  const int64_t c0 = (int64_t)blockIdx.x * AUC_CHUNK;
+  int any = 0;
+#pragma unroll
+  for (int r = 0; r < AUC_CHUNK / (AUC_TPB * 4); ++r) {
+    const int slot = (r * AUC_TPB + tid) * 4;
+    const int64_t px = c0 + slot;
+    unsigned k[4] = {AUC_SENTINEL, AUC_SENTINEL, AUC_SENTINEL, AUC_SENTINEL};
+    if (px < hw) {  // hw % 4 == 0: a 16-B load is inside the image or wholly outside
+      const f32x4 o = *reinterpret_cast<const f32x4*>(out + px);
+      const f32x4 t = *reinterpret_cast<const f32x4*>(target + px);
+      const f32x4 s = sel ? *reinterpret_cast<const f32x4*>(sel + px) : f32x4{0, 0, 0, 0};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (label_of(s[j], t[j]) == 0 && o[j] == o[j]) {
+          k[j] = auc_key(o[j]);
+          any = 1;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) keys[slot + j] = k[j];
+  }
+  any = __syncthreads_or(any);  // (also the barrier after the key stores)
+  // a chunk without a negative adds nothing to two_u; workgroup 0 still owes the class counts
+  if (!any && blockIdx.x != 0) return;
+
+  // ---- bitonic sort, ascending (sentinels last); skipped when every key is the sentinel
+  if (any) {
+    for (int k = 2; k <= AUC_CHUNK; k <<= 1) {
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        // the pairs of a pass are disjoint: all of a thread's reads first (independent, in flight
+        // together), then its exchanges
+        constexpr int PAIRS = AUC_CHUNK / 2 / AUC_TPB;
+        unsigned a[PAIRS], b[PAIRS];
+#pragma unroll
+        for (int r = 0; r < PAIRS; ++r) {
+          const int t = r * AUC_TPB + tid;
+          const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+          a[r] = keys[lo];
+          b[r] = keys[lo | j];
+        }
+#pragma unroll
+        for (int r = 0; r < PAIRS; ++r) {
+          const int t = r * AUC_TPB + tid;
+          const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+          if ((a[r] > b[r]) == ((lo & k) == 0)) {
+            keys[lo] = b[r];
+            keys[lo | j] = a[r];
+          }
+        }
+        __syncthreads();
+      }
+    }
+  }
+
+  // ---- stream the image: per considered positive, #{key < x} + #{key < x + 1}. The eight pixels of
+  // two loads are searched side by side (eight independent chains of dependent LDS reads); x = 0 (below
+  // every key) for the other pixels. The first steps read one address per wave, which LDS broadcasts.
+  // #{key < x + 1} differs from lo = #{key < x} only when keys[lo] == x, a tie: the second search runs
+  // only in waves that hold one (real-valued logits rarely tie; quantised ones pay both searches).
+  auto below = [&](const unsigned (&x)[8], unsigned (&b)[8]) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) b[q] = 0;
+    for (int st = AUC_CHUNK / 2; st > 0; st >>= 1)
+#pragma unroll
+      for (int q = 0; q < 8; ++q) b[q] += keys[b[q] + st - 1] < x[q] ? st : 0;
+    // b = the true-prefix length of `key < x` over keys[0 .. CHUNK-2]; the last key on its own
+    const unsigned last = keys[AUC_CHUNK - 1];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) b[q] += last < x[q] ? 1 : 0;
+  };
+  unsigned two_u = 0, n_pos = 0, n_neg = 0, n_nan = 0;
+  const bool counting = blockIdx.x == 0;
+  for (int64_t px0 = (int64_t)tid * 4; px0 < hw; px0 += AUC_TPB * 8) {
+    unsigned x[8];
+    bool search = false;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int64_t px = px0 + h * (AUC_TPB * 4);
+      const bool in = px < hw;  // hw % 4 == 0: a 16-B load is inside the image or wholly outside
+      const f32x4 o = in ? *reinterpret_cast<const f32x4*>(out + px) : f32x4{0, 0, 0, 0};
+      const f32x4 t = in ? *reinterpret_cast<const f32x4*>(target + px) : f32x4{2, 2, 2, 2};  // label 2: not counted
+      const f32x4 s = in && sel ? *reinterpret_cast<const f32x4*>(sel + px) : f32x4{0, 0, 0, 0};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int lab = in ? label_of(s[j], t[j]) : 2;
+        const bool nan = o[j] != o[j];
+        const bool pos = lab == 1 && !nan;
+        x[h * 4 + j] = pos ? auc_key(o[j]) : 0u;
+        search |= pos;
+        if (counting) {
+          n_pos += pos;
+          n_neg += lab == 0 && !nan;
+          n_nan += lab < 2 && nan;
+        }
+      }
+    }
+    if (any && search) {
+      unsigned lo[8];
+      below(x, lo);
+      bool tie = false;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        two_u += 2 * lo[q];
+        // lo == CHUNK: every key is below x; x == 0 equals no key (a considered key is >= 0x007FFFFF, -inf)
+        tie |= lo[q] < AUC_CHUNK && keys[lo[q] < AUC_CHUNK ? lo[q] : 0] == x[q];
+      }
+      if (tie) {
+        unsigned x1[8], hi[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) x1[q] = x[q] ? x[q] + 1u : 0u;  // a considered key is <= 0xFF800000 (+inf): no wrap
+        below(x1, hi);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) two_u += hi[q] - lo[q];
+      }
+    }
+  }
+
+  // ---- per wave by shuffles, then one 64-bit integer atomic per word and workgroup
+  const int lane = tid & 63, wave = tid >> 6;
+  unsigned part[4] = {two_u, n_pos, n_neg, n_nan};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    unsigned v = part[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if (lane == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (tid < 4) {
+    unsigned long long sum = 0;
+    for (int wv = 0; wv < AUC_TPB / 64; ++wv) sum += red[wv][tid];
+    if (sum) atomicAdd(rows + blockIdx.y * 4 + tid, sum);
+  }
 }
 
 // Risk-coverage sweep: seg_metrics_kernel's counts at k selection thresholds in one pass. With the
@@ -281,6 +489,48 @@ int selunet_seg_metrics(const float* out, const float* sel, const float* target,
   hipLaunchKernelGGL(seg_metrics_kernel, dim3(grid), dim3(IO_TPB), 0, as_stream(stream), out, sel, target, p, t_out,
                      t_sel, counts);
   return check_launch("seg_metrics");
+}
+
+// The argument rules the two per-image calls share; `fn` names the call in the message.
+static int patch_rows_args(const char* fn, const float* out, const float* sel, const float* target, int32_t n,
+                           int64_t hw, const unsigned long long* rows) {
+  SELUNET_REQUIRE(out && target && rows, "%s: null out, target or rows", fn);
+  SELUNET_REQUIRE(n >= 1, "%s: n must be >= 1 (got %d)", fn, n);
+  SELUNET_REQUIRE(hw >= 1 && hw % 4 == 0 && hw <= PATCH_MAX_HW,
+                  "%s: hw must be a multiple of 4 in [4, 2^20] (got %lld)", fn, (long long)hw);
+  SELUNET_REQUIRE(((uintptr_t)out & 15) == 0 && ((uintptr_t)target & 15) == 0 && ((uintptr_t)sel & 15) == 0,
+                  "%s: inputs must be 16-B aligned", fn);
+  SELUNET_REQUIRE(((uintptr_t)rows & 7) == 0, "%s: rows must be 8-B aligned", fn);
+  return SELUNET_OK;
+}
+
+int selunet_seg_metrics_rows(const float* out, const float* sel, const float* target, int32_t n, int64_t hw,
+                             float t_out, float t_sel, unsigned long long* rows, void* stream) {
+  if (int rc = patch_rows_args("seg_metrics_rows", out, sel, target, n, hw, rows)) return rc;
+  // at least four 16-B loads per thread before a workgroup's five closing atomics
+  const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(hw / 4, IO_TPB * 4), 64));
+  for (int32_t i0 = 0; i0 < n; i0 += PATCH_GRID_Y) {  // a grid's y dimension is 16 bits wide
+    const int64_t o = (int64_t)i0 * hw;
+    hipLaunchKernelGGL(seg_metrics_rows_kernel, dim3(gx, (unsigned)std::min(n - i0, PATCH_GRID_Y)), dim3(IO_TPB), 0,
+                       as_stream(stream), out + o, sel ? sel + o : nullptr, target + o, hw, t_out, t_sel,
+                       rows + (int64_t)i0 * 6);
+  }
+  return check_launch("seg_metrics_rows");
+}
+
+int selunet_patch_auc(const float* out, const float* sel, const float* target, int32_t n, int64_t hw, float t_sel,
+                      unsigned long long* rows, void* stream) {
+  if (int rc = patch_rows_args("patch_auc", out, sel, target, n, hw, rows)) return rc;
+  const unsigned gx = (unsigned)cdiv(hw, (int64_t)AUC_CHUNK);
+  // images per launch: blockIdx.y's 16 bits, and at most 2^31 threads in a grid
+  const int32_t per = (int32_t)std::min<int64_t>(PATCH_GRID_Y, ((int64_t)1 << 31) / ((int64_t)gx * AUC_TPB));
+  for (int32_t i0 = 0; i0 < n; i0 += per) {
+    const int64_t o = (int64_t)i0 * hw;
+    hipLaunchKernelGGL(patch_auc_kernel, dim3(gx, (unsigned)std::min(n - i0, per)), dim3(AUC_TPB), 0,
+                       as_stream(stream), out + o, sel ? sel + o : nullptr, target + o, hw, t_sel,
+                       rows + (int64_t)i0 * 4);
+  }
+  return check_launch("patch_auc");
 }
 
 int selunet_seg_metrics_sweep(const float* out, const float* sel, const float* target, int64_t p, float t_out,

@@ -18,6 +18,10 @@ Risk-coverage sweep (MI355X path only): --s_cut_off_sweep F [F ...] or --s_cut_o
 every selection cut-off of the list in the same single pass (`metrics.SelectiveSweep`, counts equal to
 a run with that --s_cut_off alone) and writes risk_coverage.json / .csv next to performance.json;
 --target_coverage C adds the largest cut-off of the list whose coverage is still >= C.
+Per-patch report (MI355X path only): --patch_report 1 writes one row per test patch from the same pass
+(`metrics.PatchReport`: confusion matrix, the reference's unused `get_performance` metrics of
+utils/compute_metric.py:93-148 with an exact ROC AUC of the logit; with --select_eval also over the
+selected pixels) to patch_performance.csv and a summary to patch_performance.json.
 A single process evaluates on the first id of --local_rank (the reference's DataParallel split
 of an eval batch changes nothing in eval mode).
 """
@@ -63,6 +67,8 @@ def parse_arguments(argv=None):
                        help='N: sweep the N+1 cut-offs linspace(0, 1, N+1) (N <= 255)')
     parser.add_argument('--target_coverage', type=float, default=None,
                         help='with a sweep: report the largest cut-off whose coverage is >= this')
+    parser.add_argument('--patch_report', type=bool, default=False,
+                        help='write one row per test patch (patch_performance.csv / .json)')
     args = parser.parse_args(argv)
     if args.s_cut_off_steps is not None and not 1 <= args.s_cut_off_steps <= 255:
         parser.error('--s_cut_off_steps: N must be in [1, 255]')
@@ -126,6 +132,11 @@ def evaluate(args):
                        s_cut_off=args.s_cut_off, output_scale=args.single_scale)
     sweep = None if cut_offs is None else MT.SelectiveSweep(device, cut_offs, rule="eval", cut_off=args.cut_off,
                                                             output_scale=args.single_scale)
+    report = None
+    if getattr(args, "patch_report", False):
+        report = MT.PatchReport(device, selective=bool(args.select_eval), rule="eval", cut_off=args.cut_off,
+                                s_cut_off=args.s_cut_off, output_scale=args.single_scale)
+    seen = 0  # patches fed so far: the loader walks the set in order
     print("Model Prediction...")
     with torch.no_grad():
         for x, target in loader:
@@ -154,6 +165,11 @@ def evaluate(args):
             ev.add_batch(output, target, selection)
             if sweep is not None:
                 sweep.add_batch(output, target, selection)
+            if report is not None:
+                n = output.shape[0]
+                report.add_batch(output, target, selection,
+                                 ids=None if ds.ids is None else list(ds.ids[seen:seen + n]))
+                seen += n
     cm = ev.confusion_matrix()
     selected, total = ev.selected_total()
     prec, rec = MT.precision(cm), MT.recall(cm)
@@ -178,7 +194,28 @@ def evaluate(args):
         json.dump(res, fh, indent=1)
     if sweep is not None:
         res = dict(res, risk_coverage=report_sweep(sweep.curve(), args.target_coverage, args.save_dir))
+    if report is not None:
+        res = dict(res, patch_report=report_patches(report.rows(), args.save_dir))
     return res
+
+
+def report_patches(rows, save_dir):
+    """Print the per-patch summary and write patch_performance.csv (one row per patch, floats by repr)
+    and patch_performance.json (the summary)."""
+    from . import metrics as MT
+
+    doc = MT.patch_report_summary(rows)
+    print(f'    per-patch report: {doc["patches"]} patches, {doc["nan_auc"]} without an AUC (one class only), '
+          f'AUC mean {doc["mean_auc"]:.6f} median {doc["median_auc"]:.6f}')
+    os.makedirs(save_dir, exist_ok=True)
+    cols = MT.patch_report_columns(rows)
+    with open(os.path.join(save_dir, "patch_performance.csv"), "w") as fh:
+        fh.write(",".join(cols) + "\n")
+        for r in rows:
+            fh.write(",".join(repr(r[c]) if isinstance(r[c], float) else str(r[c]) for c in cols) + "\n")
+    with open(os.path.join(save_dir, "patch_performance.json"), "w") as fh:
+        json.dump(doc, fh, indent=1)
+    return dict(doc, rows=rows)
 
 
 CSV_COLUMNS = ("s_cut_off", "coverage", "rejection_ratio", "selected", "total", "risk", "Acc", "mIoU")
@@ -221,10 +258,12 @@ def report_sweep(curve, target_coverage, save_dir):
 def main(argv=None):
     args = parse_arguments(sys.argv[1:] if argv is None else argv)
     print('')
-    shown = args
-    if sweep_cut_offs(args) is None:  # without a sweep the printed line is what it was before these flags
-        shown = argparse.Namespace(**{k: v for k, v in vars(args).items()
-                                      if k not in ('s_cut_off_sweep', 's_cut_off_steps', 'target_coverage')})
+    hidden = ()  # without a sweep / a patch report the printed line is what it was before these flags
+    if sweep_cut_offs(args) is None:
+        hidden += ('s_cut_off_sweep', 's_cut_off_steps', 'target_coverage')
+    if not args.patch_report:
+        hidden += ('patch_report',)
+    shown = argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden})
     print('args={}\n'.format(shown))
     evaluate(args)
     return 0

@@ -16,6 +16,11 @@ the selected/total pixel counts, accumulated as uint64 across batches.
 `SelectiveSweep` does the same for a sorted list of selection cut-offs in one pass
 (`selunet_seg_metrics_sweep`): the risk-coverage curve, and `cut_off_for_coverage` to calibrate the
 cut-off to a wanted coverage.
+
+`PatchReport` keeps one row per patch in the same pass (`selunet_seg_metrics_rows`,
+`selunet_patch_auc`): the counts per image and the exact integer Mann-Whitney statistic of the
+prediction logit, from which `patch_performance` forms the reference's unused `get_performance`
+(utils/compute_metric.py:93-148) — accuracy, recall, precision, f1 score and ROC AUC per patch.
 """
 from __future__ import annotations
 
@@ -237,3 +242,128 @@ def cut_off_for_coverage(curve, target):
     the cut-off); None when even the smallest cut-off selects less."""
     ok = [r["s_cut_off"] for r in curve if r["coverage"] >= target]
     return max(ok) if ok else None
+
+
+# ----------------------------------------------------------------------------- per-patch report
+PATCH_METRICS = ("accuracy", "recall", "precision", "f1_score", "auc_score")
+PATCH_COUNTS = ("cm00", "cm01", "cm10", "cm11", "n_pos", "n_neg", "two_u", "n_nan")
+
+
+def patch_performance(cm, two_u, n_pos, n_neg) -> dict:
+    """The reference's `get_performance` (utils/compute_metric.py:93-148) from one patch's integers:
+    cm[label][pred] the 2x2 confusion matrix, two_u / n_pos / n_neg of `selunet_patch_auc`. Its rules
+    as written, in Python numbers like its own `len()` ratios: accuracy = (TP+TN)/(C1+C0) (NaN where
+    the reference would divide by zero), recall NaN without a label-1 pixel, precision NaN without a
+    predicted-1 pixel; f1 = 2rp/(r+p) whenever r + p != 0 — its `recall != np.NaN` guard is always
+    true, so a NaN recall or precision propagates and r + p == 0 leaves NaN; AUC = two_u /
+    (2 n_pos n_neg), ties at one half as `roc_auc_score`, NaN when a class is missing (its try/except)."""
+    (tn, fp), (fn, tp) = ((int(v) for v in row) for row in cm)
+    c1, c0, p1 = fn + tp, tn + fp, fp + tp
+    nan = float("nan")
+    accuracy = (tp + tn) / (c1 + c0) if c1 + c0 else nan
+    recall = tp / c1 if c1 else nan
+    precision = tp / p1 if p1 else nan
+    f1 = nan
+    if recall + precision != 0:
+        f1 = 2 * recall * precision / (recall + precision)
+    n_pos, n_neg = int(n_pos), int(n_neg)
+    auc = int(two_u) / (2 * n_pos * n_neg) if n_pos and n_neg else nan
+    return {"accuracy": accuracy, "recall": recall, "precision": precision, "f1_score": f1, "auc_score": auc}
+
+
+def patch_row(counts, auc, prefix="") -> dict:
+    """The report fields of one patch from its six `selunet_seg_metrics_rows` counts and its four
+    `selunet_patch_auc` words."""
+    cm = [[int(counts[0]), int(counts[1])], [int(counts[2]), int(counts[3])]]
+    two_u, n_pos, n_neg, n_nan = (int(v) for v in auc)
+    row = {"cm00": cm[0][0], "cm01": cm[0][1], "cm10": cm[1][0], "cm11": cm[1][1], "n_pos": n_pos, "n_neg": n_neg,
+           "two_u": two_u, "n_nan": n_nan}
+    row.update(patch_performance(cm, two_u, n_pos, n_neg))
+    return {prefix + k: v for k, v in row.items()}
+
+
+class PatchReport:
+    """One row per patch in the pass eval already makes: per batch, `selunet_seg_metrics_rows` (the
+    Evaluator's counts per image) and `selunet_patch_auc` (the exact integer Mann-Whitney statistic of
+    the prediction logit) over all pixels and, with `selective`, again over the selected ones. The
+    per-batch row tensors stay on the device (no host synchronisation per batch); `rows()` copies once."""
+
+    def __init__(self, device, selective: bool, rule: str = "eval", cut_off: float = 0.5,
+                 s_cut_off: float = 0.5, output_scale: str = "sigmoid"):
+        self.device = device
+        self.selective = bool(selective)
+        self.t_out = logit_threshold(rule, cut_off, output_scale)
+        self.t_sel = logit_threshold(rule, s_cut_off, output_scale)
+        self.reset()
+
+    def reset(self):
+        self._batches = []  # (n, device int64 tensor [passes][n*6 + n*4] of uint64 bits)
+        self._ids = []
+
+    def add_batch(self, output: torch.Tensor, target: torch.Tensor, selection: torch.Tensor | None = None, ids=None):
+        for name, t in (("output", output), ("target", target), ("selection", selection)):
+            if t is not None and (t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise RuntimeError(f"PatchReport.add_batch: {name} must be a contiguous cuda fp32 tensor")
+        if output.dim() != 3:
+            raise ValueError(f"PatchReport.add_batch: output must be (N, H, W), got {tuple(output.shape)}")
+        if target.shape != output.shape or (selection is not None and selection.shape != output.shape):
+            raise ValueError("PatchReport.add_batch: output, target and selection must have the same shape")
+        if self.selective and selection is None:
+            raise ValueError("selective PatchReport needs the selection logits")
+        n, hw = output.shape[0], output.shape[1] * output.shape[2]
+        if ids is not None and len(ids) != n:
+            raise ValueError(f"PatchReport.add_batch: {len(ids)} ids for {n} patches")
+        passes = [None, selection] if self.selective else [None]
+        buf = torch.zeros(len(passes), n * 10, dtype=torch.int64, device=output.device)
+        stream = K.stream_ptr()
+        for k, sel in enumerate(passes):
+            K.call("selunet_seg_metrics_rows", K.ptr(output), K.ptr(sel), K.ptr(target), n, hw, self.t_out,
+                   self.t_sel, buf[k].data_ptr(), stream)
+            K.call("selunet_patch_auc", K.ptr(output), K.ptr(sel), K.ptr(target), n, hw, self.t_sel,
+                   buf[k].data_ptr() + n * 6 * 8, stream)
+        self._batches.append((n, buf))
+        self._ids.extend([None] * n if ids is None else [str(i) for i in ids])
+
+    def rows(self) -> list:
+        if not self._batches:
+            return []
+        host = torch.cat([b.reshape(-1) for _, b in self._batches]).cpu().numpy()
+        passes = 2 if self.selective else 1
+        rows, at = [], 0
+        for n, _ in self._batches:
+            part = host[at:at + passes * n * 10].reshape(passes, n * 10)
+            at += passes * n * 10
+            for i in range(n):
+                index = len(rows)
+                counts, auc = part[0, :n * 6].reshape(n, 6)[i], part[0, n * 6:].reshape(n, 4)[i]
+                row = {"index": index, "id": self._ids[index] if self._ids[index] is not None else f"patch_{index}",
+                       "pixels": int(counts[5])}
+                row.update(patch_row(counts, auc))
+                if self.selective:
+                    counts, auc = part[1, :n * 6].reshape(n, 6)[i], part[1, n * 6:].reshape(n, 4)[i]
+                    row["selected"] = int(counts[4])
+                    row["coverage"] = row["selected"] / row["pixels"]
+                    row.update(patch_row(counts, auc, prefix="sel_"))
+                rows.append(row)
+        return rows
+
+
+def patch_report_columns(rows) -> tuple:
+    """Column order of patch_performance.csv for these rows (with or without the selection fields)."""
+    cols = ("index", "id", "pixels") + PATCH_COUNTS + PATCH_METRICS
+    if rows and "selected" in rows[0]:
+        cols += ("selected", "coverage") + tuple("sel_" + c for c in PATCH_COUNTS + PATCH_METRICS)
+    return cols
+
+
+def patch_report_summary(rows) -> dict:
+    """Number of patches, of patches with a NaN AUC, and the mean and median of the finite AUCs (NaN
+    when there is none); with selection the same over the selected pixels' AUCs."""
+    doc = {"patches": len(rows)}
+    for prefix in ("", "sel_") if rows and "selected" in rows[0] else ("",):
+        auc = np.array([r[prefix + "auc_score"] for r in rows], np.float64)
+        finite = auc[np.isfinite(auc)]
+        doc[prefix + "nan_auc"] = int(len(auc) - len(finite))
+        doc[prefix + "mean_auc"] = float(finite.mean()) if len(finite) else float("nan")
+        doc[prefix + "median_auc"] = float(np.median(finite)) if len(finite) else float("nan")
+    return doc
