@@ -196,8 +196,12 @@ const char* selunet_conv3x3_wino_kernel_name(int32_t n_cols, int32_t mode, int32
  * step; the dropped l_a*l_b is below 2^-22 of the product). Measured relative RMS error against
  * fp64 at K = 576..4608 is at or below the exact fp32 MFMA's (tools/split_probe.hip). Operand
  * ranges: amax0 / amax1 (device words, amax1 only for a two-source gather) bound |source value
- * after its BN+ReLU transform|: selunet_act_bound for a BN+ReLU source, the producing kernel's
- * atomic max (selunet_epilogue.amax, selunet_bn_bwd_apply) otherwise. w: a
+ * after its BN+ReLU transform|. A BN+ReLU source has two producers: selunet_act_bound (or its fold
+ * into selunet_bn_stats_finalize_centered_bound) when scale / shift come from this batch's statistics
+ * (training: the Samuelson bound, a function of gamma, beta and the count alone), and selunet_act_amax,
+ * the exact maximum taken from the data, when they do not (eval mode, running statistics: nothing
+ * bounds the normalized value a priori). Any other source: the producing kernel's atomic max
+ * (selunet_epilogue.amax, selunet_bn_bwd_apply). w: a
  * SELUNET_PACK_CONV3X3_X2 pack ([n_cols][9*C] + n_cols row unscale factors). Same gathers,
  * epilogues and statistics slab rows as selunet_gemm_gather; selunet_conv3x3_x2_ok tells whether a
  * layer can take it (h, w >= 16, C and c_src0 multiples of 32, C > 32, n_cols a multiple of 64). */
@@ -274,6 +278,11 @@ int64_t selunet_conv3x3_x2_stats_rows(const selunet_gather* a, int32_t n_cols);
  * *out = max_c |gamma_c| * sqrt(count) + max_c |beta_c| bounds every element (max-pooled copies
  * included). One block; c <= 4096. */
 int selunet_act_bound(const float* gamma, const float* beta, int32_t c, int64_t count, float* out, void* stream);
+/* Exact range word of a BN+ReLU source whose (scale, shift) do not come from batch statistics (eval mode):
+ * atomic max (float bits; zeroed by the caller) over [m][c] of relu(y*scale_c + shift_c), the value the
+ * consumers' loaders stage. fp32 y, c a multiple of 4. One pass over y (m*c*4 bytes), no workspace. */
+int selunet_act_amax(const float* y, int64_t m, int32_t c, const float* scale, const float* shift,
+                     float* amax, void* stream);
 /* Rows of the stats slab selunet_gemm_gather writes for this operand (workgroup rows of the
  * kernel it dispatches to: 16x16 halo tiles for single-chunk 3x3 operands, the persistent
  * workgroups of the multi-chunk halo kernel, else 128-row tiles); -1 on error. */

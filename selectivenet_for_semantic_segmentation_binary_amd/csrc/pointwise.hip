@@ -719,6 +719,62 @@ __global__ void __launch_bounds__(256) act_bound_kernel(const float* __restrict_
   if (threadIdx.x == 0) out[0] = (red[0][0] * sq + red[1][0]) * 1.0001f;
 }
 
+// selunet_act_amax: *amax = max(*amax, max over [m][c] of relu(y * scale_c + shift_c)), one pass over y.
+// A thread walks the tensor as 16-B vectors v = thread + k * (grid threads), U loads in flight; CG = c / 4
+// vectors per pixel. FIXED: CG divides the grid's thread count (every power-of-two c up to 1024), so a thread
+// stays on one channel group and holds its (scale, shift) in registers; otherwise both sit in LDS and the
+// channel group advances by step = (grid threads) % CG per vector. The transform is the consumers' loader
+// expression (gemm_common.h transform16, the conv stagers): y * sc + sh, relu by fmaxf (a NaN stages as 0).
+constexpr int ACT_AMAX_U = 8;
+constexpr int ACT_AMAX_GRID = 512;  // two workgroups per CU: 16 MB of loads in flight, one atomic each
+constexpr int ACT_AMAX_CMAX = 2048;
+template <bool FIXED>
+__global__ void __launch_bounds__(TPB) act_amax_kernel(const float* __restrict__ y, int64_t nvec, int CG, int step,
+                                                       const float* __restrict__ scale,
+                                                       const float* __restrict__ shift, float* amax) {
+  constexpr int U = ACT_AMAX_U;
+  __shared__ f32x4 Ks[FIXED ? 1 : 2 * (ACT_AMAX_CMAX / 4)];
+  __shared__ float wred[TPB / 64];
+  const int64_t stride = (int64_t)gridDim.x * TPB;
+  int64_t v = blockIdx.x * (int64_t)TPB + threadIdx.x;
+  int cg = (int)(v % CG);
+  f32x4 sc, sh;
+  if constexpr (FIXED) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      sc[e] = scale[cg * 4 + e];
+      sh[e] = shift[cg * 4 + e];
+    }
+  } else {
+    float* ks = reinterpret_cast<float*>(Ks);
+    for (int i = threadIdx.x; i < 4 * CG; i += TPB) {
+      ks[i] = scale[i];
+      ks[4 * CG + i] = shift[i];
+    }
+    __syncthreads();
+  }
+  float am = 0.0f;
+  auto one = [&](const f32x4& yv) {
+    if constexpr (!FIXED) {
+      sc = Ks[cg];
+      sh = Ks[CG + cg];
+      cg += step;
+      if (cg >= CG) cg -= CG;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) am = fmaxf(am, yv[e] * sc[e] + sh[e]);
+  };
+  for (; v + (U - 1) * stride < nvec; v += U * stride) {
+    f32x4 yv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) yv[u] = Vec4<float>::load(y + (v + u * stride) * 4);
+#pragma unroll
+    for (int u = 0; u < U; ++u) one(yv[u]);
+  }
+  for (; v < nvec; v += stride) one(Vec4<float>::load(y + v * 4));
+  block_amax(amax, am, wred);
+}
+
 // =========================================================================== first-layer im2col
 // x NCHW fp32 [n][c][h][w] -> out [n*h*w][k_pad] (dtype), column tap*c + ci of a 3x3 pad-1 window,
 // zero beyond 9c. Lets the C_in = 3 layer (model.py:29) run as a dense GEMM (forward and weight
@@ -1907,6 +1963,24 @@ int selunet_act_bound(const float* gamma, const float* beta, int32_t c, int64_t 
   hipLaunchKernelGGL(act_bound_kernel, dim3(1), dim3(256), 0, as_stream(stream), gamma, beta, c,
                      (float)std::sqrt((double)count), out);
   return check_launch("act_bound");
+}
+
+int selunet_act_amax(const float* y, int64_t m, int32_t c, const float* scale, const float* shift, float* amax,
+                     void* stream) {
+  SELUNET_REQUIRE(y && scale && shift && amax && m > 0 && c > 0 && c % 4 == 0 && c <= ACT_AMAX_CMAX &&
+                      (reinterpret_cast<uintptr_t>(y) & 15) == 0,
+                  "act_amax: bad arguments (fp32 y aligned to 16 bytes, c a multiple of 4 up to %d)", ACT_AMAX_CMAX);
+  const int cg = c / 4;
+  const int64_t nvec = m * cg;
+  const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(cdiv(nvec, (int64_t)TPB * ACT_AMAX_U), ACT_AMAX_GRID));
+  const int step = (int)(blocks * TPB % cg);
+  if (step == 0)
+    hipLaunchKernelGGL(act_amax_kernel<true>, dim3((unsigned)blocks), dim3(TPB), 0, as_stream(stream), y, nvec, cg, 0,
+                       scale, shift, amax);
+  else
+    hipLaunchKernelGGL(act_amax_kernel<false>, dim3((unsigned)blocks), dim3(TPB), 0, as_stream(stream), y, nvec, cg,
+                       step, scale, shift, amax);
+  return check_launch("act_amax");
 }
 
 int selunet_bn_bwd_apply_amax(const void* dz, const void* y, int64_t m, int32_t c, const float* scale,

@@ -37,6 +37,9 @@ FIRST_KPAD = 32  # packed K of encoder_layer_1_1 (9 * C_in <= 27), see selunet_f
 # split-fp16 ("x2") kernel form of a 3x3 layer (selunet_conv3x3_x2; a split-fp16 Winograd F(2,3) form was
 # built in round 4 and retired in round 6: slower on every layer)
 X2_MODES = ("x2",)
+# conv kernels of an fp32 eval-mode forward: "exact" (Winograd / direct fp32, the default) or "split" (the
+# training forward's split-fp16 kernels, range words taken from the data: selunet_act_amax)
+EVAL_PATHS = ("exact", "split")
 
 
 def _rup(a, b):
@@ -48,7 +51,27 @@ def fp32_conv_path() -> str:
     SELUNET_WINO): "split-fp16" (the default) or "exact-fp32 (Winograd|direct)"."""
     if os.environ.get("SELUNET_X2", "1") != "0":
         return "split-fp16"
+    return _exact_conv_path()
+
+
+def _exact_conv_path() -> str:
     return "exact-fp32 (" + ("direct" if os.environ.get("SELUNET_WINO", "1") == "0" else "Winograd") + ")"
+
+
+def check_eval_path(path) -> str:
+    if path not in EVAL_PATHS:
+        raise ValueError(f"fp32_eval_path {path!r}: one of {EVAL_PATHS}")
+    return path
+
+
+def fp32_eval_conv_path(eval_path="exact", compute_dtype=torch.float32) -> str:
+    """Which kernels an eval-mode forward runs its convolutions on in this process for a module with this
+    fp32_eval_path and compute dtype: "split-fp16" only for an fp32 module that asked for "split" with
+    SELUNET_X2 not 0; otherwise the request changes nothing: "exact-fp32 (Winograd|direct)" or "bf16"."""
+    check_eval_path(eval_path)
+    if compute_dtype != torch.float32:
+        return "bf16"
+    return fp32_conv_path() if eval_path == "split" else _exact_conv_path()
 
 
 @dataclass
@@ -62,7 +85,7 @@ class BNState:
     h: int
     w: int
     c: int
-    amax: torch.Tensor = None  # range word of relu(bn(y)) (split-fp16 layers, selunet_act_bound)
+    amax: torch.Tensor = None  # range word of relu(bn(y)) (split-fp16 layers: selunet_act_bound, eval selunet_act_amax)
     name: str = ""
 
     def src(self):
@@ -250,16 +273,19 @@ class Engine:
             return False
         return self._shape_ok("selunet_conv3x3_wino_ok", name, ci, co, hw, need_dgrad)
 
-    def _x2_ok(self, name, ci, co, hw, need_dgrad, training):
-        """fp32 training layers on split-fp16 operands (selunet_conv3x3_x2). Training only: the range
-        word of a BN+ReLU input (selunet_act_bound) holds for batch statistics."""
-        if not (self.x2 and training) or hw is None or name == "encoder_layer_1_1":
+    def _x2_ok(self, name, ci, co, hw, need_dgrad, training, eval_split=False):
+        """fp32 layers on split-fp16 operands (selunet_conv3x3_x2): every training forward, and an
+        eval-mode forward that asked for the "split" path (eval_split). The two differ in the range word
+        of a BN+ReLU input: the Samuelson bound (selunet_act_bound) holds for batch statistics only, so
+        an eval forward takes the exact maximum from the data (selunet_act_amax)."""
+        if not (self.x2 and (training or eval_split)) or hw is None or name == "encoder_layer_1_1":
             return False
         return self._shape_ok("selunet_conv3x3_x2_ok", name, ci, co, hw, need_dgrad)
 
-    def pack_weights(self, P, need_dgrad=True, hw=None, training=False, heads=()):
+    def pack_weights(self, P, need_dgrad=True, hw=None, training=False, heads=(), eval_split=False):
         """fp32 master weights -> GEMM operand layouts in the compute dtype (one launch for all);
-        fp32 layers at input resolution hw get the split-fp16 (training) or Winograd operands.
+        fp32 layers at input resolution hw get the split-fp16 (training, or eval with eval_split) or
+        Winograd operands.
         heads: (name, channels) of the output heads whose weights / biases are gathered, in the same
         launch, into the contiguous fp32 operands of the heads kernel (packs["heads"] = (w, b)).
         Returns name -> WPack."""
@@ -270,7 +296,7 @@ class Engine:
             w = P[f"{name}.0.weight"]
             ci = w.shape[1]
             dg = None
-            if self._x2_ok(name, ci, co, hw, need_dgrad, training):
+            if self._x2_ok(name, ci, co, hw, need_dgrad, training, eval_split):
                 mode, kpad, kind = "x2", 9 * ci, K.PACK_CONV3X3_X2
                 fwd = K.keep(torch.empty(co * kpad + co, dtype=torch.float32, device=dev))
                 if need_dgrad:
@@ -414,9 +440,13 @@ class Engine:
         # holds for statistics over THIS rank's M values (per-rank BatchNorm, DataParallel replica
         # semantics); a synchronized BatchNorm would need M = the global count here.
         # (fp32 training folds it into the centered finalize: max_c |gamma_c| sqrt(M) + |beta_c|)
+        # An eval-mode forward on the split-fp16 kernels (running statistics: no a-priori bound) takes the
+        # exact maximum of the staged values from the data, one pass over y.
         if ctx.x2:
             st.amax = self._word(ctx, "act:" + name)
-            if not (ctx.training and self.dt == torch.float32):
+            if not ctx.training:
+                K.call("selunet_act_amax", K.ptr(y), M, co, K.ptr(scale), K.ptr(shift), K.ptr(st.amax), self.stream)
+            elif self.dt != torch.float32:
                 K.call("selunet_act_bound", K.ptr(P[f"{name}.1.weight"]), K.ptr(P[f"{name}.1.bias"]), co, M,
                        K.ptr(st.amax), self.stream)
         ctx.bn[name] = st
@@ -476,10 +506,13 @@ class Engine:
         if ctx is not None and ctx.entry is not None:
             ctx.entry.busy = False
 
-    def forward(self, x, P, B, selective, training, need_backward=False, ce_heads=None):
+    def forward(self, x, P, B, selective, training, need_backward=False, ce_heads=None, eval_path="exact"):
         """x: [N, Cin, H, W] fp32 contiguous. Returns (heads tuple, ctx); the heads are new tensors:
         [N, H, W] logits for UNet_B, or, with ce_heads = [(head, channels)] (the CE `UNet`),
-        NCHW [N, channels, H, W] logits per head."""
+        NCHW [N, channels, H, W] logits per head. eval_path (EVAL_PATHS): the conv kernels of an eval-mode
+        forward; "split" takes effect on an fp32 engine with SELUNET_X2 not 0 and is otherwise (and in
+        training mode) the same forward as "exact"."""
+        eval_split = check_eval_path(eval_path) == "split" and self.x2 and not training
         assert x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32
         n, cin, H, W = x.shape
         if H % 8 or W % 8:
@@ -490,11 +523,12 @@ class Engine:
         else:
             ce_heads = tuple(ce_heads)
             outs = tuple(torch.empty(n, c, H, W, dtype=torch.float32, device=x.device) for _, c in ce_heads)
-        e = self._entry_for(self._signature(x, P, B, selective, training, need_backward) + (ce_heads,)) \
+        # (the effective path is part of the signature: a toggled module never replays the other path's plan)
+        e = self._entry_for(self._signature(x, P, B, selective, training, need_backward) + (ce_heads, eval_split)) \
             if self.plans_enabled else None
         slots = {"x": x, **{f"out{i}": o for i, o in enumerate(outs)}}
         if e is None:
-            ctx = self._forward_impl(x, P, B, selective, training, need_backward, outs, ce_heads)
+            ctx = self._forward_impl(x, P, B, selective, training, need_backward, outs, ce_heads, eval_split)
         elif e.plan is not None:
             e.plan.replay(slots)
             ctx = e.ctx
@@ -502,14 +536,14 @@ class Engine:
         else:
             plan = K.Plan(slots)
             with K.recording(plan):
-                ctx = self._forward_impl(x, P, B, selective, training, need_backward, outs, ce_heads)
+                ctx = self._forward_impl(x, P, B, selective, training, need_backward, outs, ce_heads, eval_split)
             e.plan, e.ctx = plan, ctx
             ctx.entry = e
         if e is not None and training and need_backward:
             e.busy = True
         return outs, ctx
 
-    def _forward_impl(self, x, P, B, selective, training, need_backward, outs, ce_heads=None):
+    def _forward_impl(self, x, P, B, selective, training, need_backward, outs, ce_heads=None, eval_split=False):
         n, cin, H, W = x.shape
         ctx = Ctx(self.dt, training, selective, (n, cin, H, W), x=x)
         ctx.ce_heads = ce_heads
@@ -519,7 +553,7 @@ class Engine:
             raise ValueError(f"the heads have {sum(c for _, c in heads)} output channels; the MI355X heads kernel "
                              "takes at most 8")
         ctx.wpack = self.pack_weights(P, need_dgrad=training and need_backward, hw=(H, W), training=training,
-                                      heads=heads)
+                                      heads=heads, eval_split=eval_split)
         hw, hb = ctx.wpack.pop("heads")
         ctx.x2 = any(wp.mode in X2_MODES for wp in ctx.wpack.values())
         if ctx.x2:  # the operand range words of this step, zeroed for their atomic-max producers

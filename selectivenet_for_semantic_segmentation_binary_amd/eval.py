@@ -22,6 +22,9 @@ Per-patch report (MI355X path only): --patch_report 1 writes one row per test pa
 (`metrics.PatchReport`: confusion matrix, the reference's unused `get_performance` metrics of
 utils/compute_metric.py:93-148 with an exact ROC AUC of the logit; with --select_eval also over the
 selected pixels) to patch_performance.csv and a summary to patch_performance.json.
+fp32 conv path (MI355X path only): --fp32_path split runs the fp32 forward on the training forward's
+split-fp16 kernels (`UNet_B(fp32_eval_path="split")`); the default, exact, keeps the exact
+fp32 kernels. Not with --compute_dtype bf16.
 A single process evaluates on the first id of --local_rank (the reference's DataParallel split
 of an eval batch changes nothing in eval mode).
 """
@@ -69,7 +72,11 @@ def parse_arguments(argv=None):
                         help='with a sweep: report the largest cut-off whose coverage is >= this')
     parser.add_argument('--patch_report', type=bool, default=False,
                         help='write one row per test patch (patch_performance.csv / .json)')
+    parser.add_argument('--fp32_path', type=str, default='exact', choices=['exact', 'split'],
+                        help='conv kernels of the fp32 forward: exact fp32, or the split-fp16 kernels of training')
     args = parser.parse_args(argv)
+    if args.fp32_path == 'split' and args.compute_dtype == 'bf16':
+        parser.error('--fp32_path split is an fp32 path: not with --compute_dtype bf16')
     if args.s_cut_off_steps is not None and not 1 <= args.s_cut_off_steps <= 255:
         parser.error('--s_cut_off_steps: N must be in [1, 255]')
     if args.target_coverage is not None and sweep_cut_offs(args) is None:
@@ -119,7 +126,8 @@ def evaluate(args):
     for name, a in zip(model_list, arch):
         if args.info_print:
             print(f'    {os.path.join(args.model_dir, name)} - {a} / SelectiveNet: {args.selective}')
-        net = S.UNet_B(args.input_type, selective=args.selective, compute_dtype=dt)
+        net = S.UNet_B(args.input_type, selective=args.selective, compute_dtype=dt,
+                       fp32_eval_path=getattr(args, "fp32_path", "exact"))
         net_utils.net_test_load(os.path.join(args.model_dir, name), net)
         nets.append(net.to(device).train(False))
     if len(nets) > 1 and args.selective:
@@ -258,11 +266,13 @@ def report_sweep(curve, target_coverage, save_dir):
 def main(argv=None):
     args = parse_arguments(sys.argv[1:] if argv is None else argv)
     print('')
-    hidden = ()  # without a sweep / a patch report the printed line is what it was before these flags
+    hidden = ()  # without a sweep / a patch report / the split path the printed line is what it was before these flags
     if sweep_cut_offs(args) is None:
         hidden += ('s_cut_off_sweep', 's_cut_off_steps', 'target_coverage')
     if not args.patch_report:
         hidden += ('patch_report',)
+    if args.fp32_path == 'exact':
+        hidden += ('fp32_path',)
     shown = argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden})
     print('args={}\n'.format(shown))
     evaluate(args)

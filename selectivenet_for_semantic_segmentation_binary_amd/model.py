@@ -11,6 +11,10 @@ Extra keyword (not in the reference): `compute_dtype` — torch.float32 (default
 configuration: fp32 tensors; in training the 3x3 convolutions run on split-fp16 operands with an
 error at or below the exact fp32 MFMA's, SELUNET_X2=0 selects exact fp32 MFMA products) or
 torch.bfloat16 (bf16 operands, fp32 accumulation, statistics, losses and master weights).
+`fp32_eval_path` — "exact" (default: eval-mode forwards of an fp32 module run the exact fp32 Winograd /
+direct kernels) or "split" (they run the training forward's split-fp16 kernels, with operand range words
+taken from the data). Also an attribute: `net.fp32_eval_path = "split"`. A bf16 module, or
+SELUNET_X2=0, runs its usual eval kernels whatever this says (`engine.fp32_eval_conv_path` reports which).
 """
 from __future__ import annotations
 
@@ -23,7 +27,7 @@ import torch.nn as nn
 from . import _lib as K
 from . import layout as LY
 from . import parallel
-from .engine import Engine
+from .engine import Engine, check_eval_path
 
 
 class _Conv2dParams(nn.Module):
@@ -98,7 +102,7 @@ class _UNetBFunction(torch.autograd.Function):
         eng = module._engine()
         need_bwd = training and any(ctx.needs_input_grad[2:])
         outs, ectx = eng.forward(x.contiguous(), P, B, module.selective, training, need_backward=need_bwd,
-                                 ce_heads=module._ce_heads)
+                                 ce_heads=module._ce_heads, eval_path=module.fp32_eval_path)
         if need_bwd:
             ctx.ectx = ectx
             ctx.eng = eng
@@ -141,8 +145,10 @@ class _UNetBase(nn.Module):
     """The encoder-decoder shared by UNet_B (model.py:18-103) and the CE UNet (model.py:105-191);
     they differ only in the 1x1 heads (n_cls None: 1-channel heads)."""
 
-    def __init__(self, input_type="RGB", selective=False, compute_dtype=torch.float32, n_cls=None):
+    def __init__(self, input_type="RGB", selective=False, compute_dtype=torch.float32, n_cls=None,
+                 fp32_eval_path="exact"):
         super().__init__()
+        self.fp32_eval_path = fp32_eval_path
         self.selective = selective
         input_ch = LY.input_channels(input_type)
         self.compute_dtype = compute_dtype
@@ -173,6 +179,14 @@ class _UNetBase(nn.Module):
         self._param_names = [n for n, _ in self.named_parameters()]
         self._engines = {}
 
+    @property
+    def fp32_eval_path(self):
+        return self._fp32_eval_path
+
+    @fp32_eval_path.setter
+    def fp32_eval_path(self, path):
+        self._fp32_eval_path = check_eval_path(path)
+
     def _engine(self):
         e = self._engines.get(self.compute_dtype)
         if e is None:
@@ -194,8 +208,8 @@ class UNet_B(_UNetBase):
     """model.py:18-103 UNet for BCE loss, optionally SelectiveNet (selection + aux heads):
     [N, C_in, H, W] -> (N, H, W) logits, or (out, select, aux) each (N, H, W)."""
 
-    def __init__(self, input_type="RGB", selective=False, compute_dtype=torch.float32):
-        super().__init__(input_type, selective, compute_dtype)
+    def __init__(self, input_type="RGB", selective=False, compute_dtype=torch.float32, fp32_eval_path="exact"):
+        super().__init__(input_type, selective, compute_dtype, fp32_eval_path=fp32_eval_path)
 
 
 class UNet(_UNetBase):
@@ -204,8 +218,9 @@ class UNet(_UNetBase):
     select (N, 2, H, W) (model.py:182-189). n_cls + 2 + n_cls <= 8 output channels (n_cls <= 3
     selective, <= 8 otherwise) — the reference trains with n_cls = 2 (train.py:23)."""
 
-    def __init__(self, input_type="RGB", n_cls=2, selective=False, compute_dtype=torch.float32):
+    def __init__(self, input_type="RGB", n_cls=2, selective=False, compute_dtype=torch.float32,
+                 fp32_eval_path="exact"):
         if n_cls < 1 or sum(c for _, c in LY.head_channels(selective, n_cls)) > 8:
             raise ValueError(f"n_cls={n_cls}: the heads may have at most 8 output channels in total")
-        super().__init__(input_type, selective, compute_dtype, n_cls=n_cls)
+        super().__init__(input_type, selective, compute_dtype, n_cls=n_cls, fp32_eval_path=fp32_eval_path)
         self.n_cls = n_cls

@@ -25,6 +25,8 @@ What differs, by design:
     GPU. input_type 'RGB', 'GH' or 'H_RGB'; model_arch 'UNet_B' with loss 'BCElogit', or the CE `UNet`
     (model_arch 'UNet', loss 'CE', n_cls 2: CrossEntropyLoss aux + calc_selective_risk_image, argmax
     masks as train.py:207-219).
+  * `--valid_fp32_path split` runs the per-epoch validation forwards (net.eval()) of an fp32 run on the
+    training forward's split-fp16 kernels (`fp32_eval_path`); training steps are unaffected.
   * TensorBoard scalars are written when torch.utils.tensorboard is importable, otherwise as JSON
     lines in `{log_dir}/{train,valid}/scalars.jsonl`.
 """
@@ -77,7 +79,13 @@ def parse_arguments(argv=None):
     parser.add_argument('--steps_per_epoch', type=int, default=0, help='cap on training batches per epoch (0 = all)')
     parser.add_argument('--val_steps', type=int, default=0, help='cap on validation batches per epoch (0 = all)')
     parser.add_argument('--quiet', action='store_true')
-    return parser.parse_args(argv)
+    parser.add_argument('--valid_fp32_path', type=str, default='exact', choices=['exact', 'split'],
+                        help="conv kernels of the fp32 validation forwards: exact fp32, or the training forward's "
+                             "split-fp16 kernels (the validation loop only)")
+    args = parser.parse_args(argv)
+    if args.valid_fp32_path == 'split' and args.compute_dtype == 'bf16':
+        parser.error('--valid_fp32_path split is an fp32 path: not with --compute_dtype bf16')
+    return args
 
 
 # ----------------------------------------------------------------------------- process launch
@@ -205,11 +213,13 @@ def train(args, ckpt_dir, log_dir):
     torch.manual_seed(args.seed)
     dt = torch.bfloat16 if args.compute_dtype == 'bf16' else torch.float32
     if ce:
-        net = S.UNet(args.input_type, args.n_cls, selective=args.selective, compute_dtype=dt)
+        net = S.UNet(args.input_type, args.n_cls, selective=args.selective, compute_dtype=dt,
+                     fp32_eval_path=args.valid_fp32_path)
         loss_A = S.CrossEntropyLoss()
         loss_S = S.calc_selective_risk_image if args.selective else None
     else:
-        net = S.UNet_B(args.input_type, selective=args.selective, compute_dtype=dt)
+        net = S.UNet_B(args.input_type, selective=args.selective, compute_dtype=dt,
+                       fp32_eval_path=args.valid_fp32_path)
         loss_A = S.BCEWithLogitsLoss()
         loss_S = S.calc_selective_risk_image_b if args.selective else None
 
@@ -345,7 +355,10 @@ def main(argv=None):
         return spawn(argv, args.local_rank)
     if not args.quiet and os.environ.get("RANK", "0") == "0":
         print('')
-        print('args={}\n'.format(args))
+        # (the default validation path is not printed: the line is what it was before the flag)
+        shown = argparse.Namespace(**{k: v for k, v in vars(args).items()
+                                      if not (k == 'valid_fp32_path' and v == 'exact')})
+        print('args={}\n'.format(shown))
     ckpt_dir = f'{args.model_dir}/{args.fold}-fold/checkpoint'
     log_dir = f'{args.model_dir}/{args.fold}-fold/log'
     train(args, ckpt_dir, log_dir)
