@@ -27,7 +27,7 @@ import torch
 import torch.nn.functional as F
 
 from selectivenet_for_semantic_segmentation_binary_amd import _lib as K
-from tests.test_gpu_kernels import bn_fold, gen, halo_wgs, nchw, nhwc, pack, rel  # noqa: F401
+from tests.test_gpu_kernels import bn_fold, gen, halo_wgs, kernel_option, nchw, nhwc, pack, rel  # noqa: F401
 from tests.test_gpu_wino import pack_wino
 from tests.test_gpu_x2 import pack_x2, tile_queue, word, x2d  # noqa: F401
 
@@ -50,10 +50,14 @@ def fp32_run(kernel, ptiles, rows):
     double and reduce the workgroup in fp64 (run = those rows, at most 8). The others stay in fp32:
       conv3x3_halo1<f32,64>  one tile, 512 threads, 64 columns: 4 rows, then 64 row groups summed in fp32;
       conv3x3_x2p<f32,128>   per 32-column quarter, 256 threads: 4 rows, then 64 row groups in fp32 (then fp64);
+      conv3x3_halo<f32,64>   (HALO_PERSIST = 0) one tile, fp32 registers, as conv3x3_halo1: 4 rows, then 64 row groups;
+      conv3x3_halo<f32,128>  the same with 128 columns: 512 / 16 = 32 row groups of 8 rows each;
       conv3x3_x2<f32,128>, conv3x3_wino<128>  fp32 registers over all tiles of the workgroup (8 rows each,
                              ceil(ptiles / rows) tiles; one with the tile queue, rows == ptiles), then 32 row groups."""
-    if kernel in ("conv3x3_halo1<f32,64>", "conv3x3_x2p<f32,128>"):
+    if kernel in ("conv3x3_halo1<f32,64>", "conv3x3_x2p<f32,128>", "conv3x3_halo<f32,64>"):
         return 4 + 64
+    if kernel == "conv3x3_halo<f32,128>":
+        return 8 + 32
     if kernel in ("conv3x3_x2<f32,128>", "conv3x3_wino<128>"):
         return 8 * -(-ptiles // rows) + 32
     assert kernel in ("gemm_gather<f32>", "conv3x3_halo_persist<f32,64>", "conv3x3_halo_persist<f32,128>",
@@ -144,6 +148,33 @@ def conv_sources(case, cin0, cin1, with_words):
 @pytest.mark.parametrize("wgs", [0, 3])
 def test_gemm_gather_shifted_stats(cin0, cin1, cout, n, h, w, wgs, halo_wgs):
     halo_wgs(wgs)
+    gemm_gather_shifted_stats_case(cin0, cin1, cout, n, h, w)
+
+
+@pytest.mark.parametrize("cin0,cin1,cout,n,h,w,kernel", [
+    (64, 0, 64, 2, 32, 32, "conv3x3_halo<f32,64>"),
+    (128, 0, 256, 2, 20, 24, "conv3x3_halo<f32,128>"),   # partial halo tiles, two column tiles
+])
+def test_gemm_gather_shifted_stats_nonpersistent(cin0, cin1, cout, n, h, w, kernel, kernel_option):
+    """The shifted statistics epilogue of the non-persistent multi-chunk halo kernel (HALO_PERSIST = 0): one slab
+    row per 16x16 tile, summed in fp32 registers over the tile (fp32_run)."""
+    kernel_option(("HALO_PERSIST", 0))
+    assert gemm_gather_shifted_stats_case(cin0, cin1, cout, n, h, w) == kernel
+    # ... and its output range word (ep.amax): the largest |stored value|, one atomic per workgroup
+    case = conv_case(cin0, cin1, cout, n, h, w)
+    fwd, _, kpad = pack(case["wt"])
+    keep, srcs, _ = conv_sources(case, cin0, cin1, False)
+    y = torch.full((n * h * w, cout), float("nan"), device=DEV)
+    am = torch.zeros(1, device=DEV)
+    ep = K.Epilogue(K.ptr(y), None, None, None, K.EP_PLAIN, 0)
+    ep.amax = K.ptr(am)
+    K.call("selunet_gemm_gather", K.gather(n, h, w, 9, *srcs), K.ptr(fwd), cout, kpad, ep, K.F32, K.stream_ptr())
+    torch.cuda.synchronize()
+    assert rel(nchw(y.cpu(), n, h, w), case["ref"]) < 1e-4
+    assert am.item() == y.abs().max().item()
+
+
+def gemm_gather_shifted_stats_case(cin0, cin1, cout, n, h, w):
     case = conv_case(cin0, cin1, cout, n, h, w)
     fwd, _, kpad = pack(case["wt"])
     keep, srcs, _ = conv_sources(case, cin0, cin1, False)
@@ -158,6 +189,7 @@ def test_gemm_gather_shifted_stats(cin0, cin1, cout, n, h, w, wgs, halo_wgs):
         K.call("selunet_gemm_gather", g, K.ptr(fwd), cout, kpad, ep, K.F32, K.stream_ptr())
 
     check_family(launch, n * h * w, cout, rows, case, stat_tol(fp32_run(kernel, ptiles, rows)), 1e-4)
+    return kernel
 
 
 @pytest.mark.parametrize("cin0,cin1,cout,n,h,w", [

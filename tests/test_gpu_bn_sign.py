@@ -25,7 +25,7 @@ from tests import test_gpu_wino as WI
 from tests import test_gpu_x2 as X2
 from tests.test_gpu_apply_fused import check_dy_fp64
 from tests.test_gpu_kernels import (bn_fold, bn_state, check_bnb_sums, check_signed_inputs, gather_wgs,  # noqa: F401
-                                    gen, halo_wgs, nchw, nhwc, rel, signed_gamma)
+                                    gen, halo_wgs, kernel_option, nchw, nhwc, rel, signed_gamma)
 from tests.test_gpu_x2 import convt_ring, tile_queue, x2d  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -154,6 +154,19 @@ def test_convT_bf16_wgrad_signed():
 
 def test_wino_wgrad_signed():
     WI.wino_wgrad_case(64, 0, 64, True, 2, 16, 16, signed=True)
+
+
+@pytest.mark.parametrize("wgs", [-1, 4])
+@pytest.mark.parametrize("nw", [12, 8])
+@pytest.mark.parametrize("tw", [16, 8])
+def test_wino_wgrad_signed_variants(tw, nw, wgs, kernel_option):
+    """The four instantiations of the Winograd weight gradient (tile width, waves) with signed scales, one tile
+    per workgroup and several (WGRAD_WGS = 4 at 2x20x36: 18 tiles as 5, 5, 5, 3 at tile width 16; 30 as
+    8, 8, 8, 6 at 8)."""
+    for name, v in (("WINO_WGRAD_TW", tw), ("WINO_WGRAD_WAVES", nw), ("WGRAD_WGS", wgs)):
+        kernel_option((name, v))
+        assert K.set_option(name, v) == v
+    WI.wino_wgrad_case(64, 0, 64, True, 2, 20, 36, signed=True)
 
 
 @pytest.mark.parametrize("cin0,cin1,cout", [(64, 0, 64), (64, 64, 128)])

@@ -72,8 +72,39 @@ def kernel_option():
 
 
 # kernel-selection alternatives the bf16 persistent-kernel tests also run under (the 16x16x32 MFMA form and
-# single-chunk layers on the persistent kernel were retired in round 6 after losing every A/B)
-BF16_VARIANTS = [None]
+# single-chunk layers on the persistent kernel were retired in round 6 after losing every A/B);
+# HALO_PERSIST = 0: the non-persistent multi-chunk halo kernel, conv3x3_halo_kernel<T, BN, false>
+BF16_VARIANTS = [None, ("HALO_PERSIST", 0)]
+
+
+def check_halo_variant(variant, n, h, w, cins, n_cols, split, dtype):
+    """Under a kernel-selection variant, before the launch: the halo-eligible operand dispatches to the kernel the
+    variant names. HALO_PERSIST = 0: conv3x3_halo<T,BN> (single-chunk inputs stay on conv3x3_halo1), one
+    statistics row per 16x16 pixel tile, and the split-fp16 / Winograd predicates answer 0 (the engine's fallback
+    to this kernel depends on that). HALO = 0: the gather GEMM."""
+    if variant is None:
+        return
+    bf = dtype == K.BF16
+    tag = "bf16" if bf else "f32"
+    fake = torch.empty(64)  # never dereferenced: the queries look at shapes only
+    g = K.gather(n, h, w, 9, *[K.source(fake, c) for c in cins])
+    mode = K.EP_SPLIT if split else K.EP_PLAIN
+    name = K.query("selunet_gemm_kernel_name", g, None, n_cols, mode, dtype).decode()
+    rows = K.query("selunet_gemm_stats_rows", g, n_cols, dtype)
+    assert K.set_option(*variant) == variant[1]  # the option reads back
+    if variant == ("HALO", 0):
+        assert name == f"gemm_gather<{tag}>"
+        assert rows == -(-n * h * w // K.GEMM_BM)
+        return
+    assert variant == ("HALO_PERSIST", 0) and h >= 16 and w >= 16
+    if sum(cins) == (64 if bf else 32):
+        assert name == f"conv3x3_halo1<{tag},64>"
+    else:
+        bn = 128 if n_cols % 128 == 0 and not (split and split % 128) else 64
+        assert name == f"conv3x3_halo<{tag},{bn}>"
+    assert rows == n * -(-h // 16) * -(-w // 16)
+    assert K.query("selunet_conv3x3_x2_ok", h, w, sum(cins), cins[0], n_cols) == 0
+    assert K.query("selunet_conv3x3_wino_ok", h, w, sum(cins), cins[0], n_cols) == 0
 
 
 def gen(*shape, seed=0, scale=1.0):
@@ -144,7 +175,7 @@ def pack(w, dt=torch.float32):
     return fwd, dg, kpad
 
 
-@pytest.mark.parametrize("cin0,cin1,cout,n,h,w,xform", [
+FWD_STATS_SHAPES = [
     (64, 0, 64, 2, 16, 16, True),
     (128, 0, 256, 1, 8, 12, False),
     (64, 64, 128, 2, 8, 8, True),      # two-source (torch.cat) gather
@@ -154,12 +185,28 @@ def pack(w, dt=torch.float32):
     (64, 64, 128, 1, 16, 48, True),    # halo kernel, two sources, BN = 128
     (128, 0, 256, 2, 20, 24, True),    # halo kernel, partial edge tiles
     (32, 0, 64, 2, 24, 20, True),      # one fp32 channel chunk: weights-resident persistent kernel
-])
+]
+
+
+@pytest.mark.parametrize("cin0,cin1,cout,n,h,w,xform", FWD_STATS_SHAPES)
 @pytest.mark.parametrize("wgs", [0, 3])
 def test_conv3x3_fwd_stats(cin0, cin1, cout, n, h, w, xform, wgs, halo_wgs):
     """wgs = 3: the persistent multi-chunk halo kernel with 3 workgroup rows, so every workgroup
     walks several (unevenly many) tiles and accumulates its statistics over them."""
     halo_wgs(wgs)
+    conv3x3_fwd_stats_case(cin0, cin1, cout, n, h, w, xform)
+
+
+@pytest.mark.parametrize("cin0,cin1,cout,n,h,w,xform", [s for s in FWD_STATS_SHAPES if s[4] >= 16 and s[5] >= 16])
+@pytest.mark.parametrize("wgs", [0, 3])
+@pytest.mark.parametrize("variant", BF16_VARIANTS[1:])
+def test_conv3x3_fwd_stats_variant(cin0, cin1, cout, n, h, w, xform, wgs, variant, halo_wgs, kernel_option):
+    """test_conv3x3_fwd_stats on its halo-sized shapes under a kernel-selection variant (the fp32 form of the
+    variant parameter of test_conv3x3_bf16_persist_fwd_stats; a function of its own so that the ids of the default
+    cases stay as they are)."""
+    halo_wgs(wgs)
+    kernel_option(variant)
+    check_halo_variant(variant, n, h, w, [cin0, cin1] if cin1 else [cin0], cout, 0, K.F32)
     conv3x3_fwd_stats_case(cin0, cin1, cout, n, h, w, xform)
 
 
@@ -213,15 +260,30 @@ def test_conv3x3_fwd_small_c_nchw():
     assert rel(nchw(y.cpu(), n, h, w), ref) < TOL
 
 
-@pytest.mark.parametrize("cin,cout,split,h,w", [(64, 64, 0, 8, 8), (128, 64, 64, 8, 8), (512, 256, 256, 8, 8),
-                                                (64, 128, 0, 8, 8), (64, 64, 0, 32, 32), (128, 64, 64, 32, 32),
-                                                (256, 128, 128, 16, 48), (64, 32, 0, 24, 20), (128, 32, 64, 16, 40)])
+DGRAD_SHAPES = [(64, 64, 0, 8, 8), (128, 64, 64, 8, 8), (512, 256, 256, 8, 8),
+                (64, 128, 0, 8, 8), (64, 64, 0, 32, 32), (128, 64, 64, 32, 32),
+                (256, 128, 128, 16, 48), (64, 32, 0, 24, 20), (128, 32, 64, 16, 40)]
+
+
+@pytest.mark.parametrize("cin,cout,split,h,w", DGRAD_SHAPES)
 @pytest.mark.parametrize("wgs", [0, 3])
 def test_conv3x3_dgrad(cin, cout, split, h, w, wgs, halo_wgs, gather_wgs):
     """wgs = 3 also sets the generic gather GEMM (the 8x8 cases, 3 row tiles at n = 6) to one workgroup
     row: one workgroup walks every tile and accumulates the column / BN-backward sums over them."""
     halo_wgs(wgs)
     gather_wgs(wgs - 2 if wgs else -1)
+    conv3x3_dgrad_case(cin, cout, split, h, w)
+
+
+@pytest.mark.parametrize("cin,cout,split,h,w", [s for s in DGRAD_SHAPES if s[3] >= 16 and s[4] >= 16])
+@pytest.mark.parametrize("wgs", [0, 3])
+@pytest.mark.parametrize("variant", BF16_VARIANTS[1:])
+def test_conv3x3_dgrad_variant(cin, cout, split, h, w, wgs, variant, halo_wgs, kernel_option):
+    """test_conv3x3_dgrad on its halo-sized shapes under a kernel-selection variant (SPLIT with the column sums,
+    PLAIN with the BN-backward sums)."""
+    halo_wgs(wgs)
+    kernel_option(variant)
+    check_halo_variant(variant, 2, h, w, [cout], cin, split, K.F32)
     conv3x3_dgrad_case(cin, cout, split, h, w)
 
 
@@ -831,6 +893,7 @@ def first_conv_wgrad_bn_case(dt, cin, n, h, w, signed=False):
     (64, 0, 128, 3, 24, 24),     # one chunk, two 64-column tiles
     (128, 128, 256, 1, 33, 40),  # two sources (torch.cat), two column tiles
     (256, 0, 512, 2, 32, 32),    # four chunks, four column tiles
+    (128, 0, 64, 2, 20, 40),     # two chunks, one 64-column tile: conv3x3_halo_persist<bf16,64> / conv3x3_halo<bf16,64>
 ])
 @pytest.mark.parametrize("wgs", [0, 3])
 @pytest.mark.parametrize("variant", BF16_VARIANTS)
@@ -839,6 +902,7 @@ def test_conv3x3_bf16_persist_fwd_stats(cin0, cin1, cout, n, h, w, wgs, variant,
     wgs = 3 makes every workgroup walk several tiles; variant: a kernel-selection option set for the test."""
     halo_wgs(wgs)
     kernel_option(variant)
+    check_halo_variant(variant, n, h, w, [cin0, cin1] if cin1 else [cin0], cout, 0, K.BF16)
     conv3x3_bf16_persist_fwd_stats_case(cin0, cin1, cout, n, h, w)
 
 
@@ -883,6 +947,7 @@ def test_conv3x3_bf16_persist_dgrad(cin, cout, split, h, w, wgs, variant, halo_w
     and the torch.cat split with the ConvTranspose2d bias column sums."""
     halo_wgs(wgs)
     kernel_option(variant)
+    check_halo_variant(variant, 2, h, w, [cout], cin, split, K.BF16)
     conv3x3_bf16_persist_dgrad_case(cin, cout, split, h, w)
 
 

@@ -15,6 +15,7 @@ import torch
 import selectivenet_for_semantic_segmentation_binary_amd as S
 import selectivenet_for_semantic_segmentation_binary_amd.layout as L
 from oracle import unet_b_cpu as O
+from selectivenet_for_semantic_segmentation_binary_amd import _lib as K
 from selectivenet_for_semantic_segmentation_binary_amd.engine import fp32_conv_path
 from selectivenet_for_semantic_segmentation_binary_amd.synthetic import make_batch
 from tests import _golden as G
@@ -322,6 +323,19 @@ def test_step_against_oracle_shapes(input_type, n, h, w, selective):
     step_against_oracle(input_type, n, h, w, selective, L.seeded_params(3, input_type, selective))
 
 
+def test_step_against_oracle_nonpersistent_halo():
+    """test_step_against_oracle_shapes at 2x32x32 with SELUNET_OPT_HALO_PERSIST = 0, set before the net (and so
+    its engine) is built and restored after: selunet_conv3x3_x2_ok / _wino_ok answer 0, every halo-sized 3x3
+    layer falls back to conv3x3_halo<f32,BN> with one statistics row per 16x16 tile, and the engine has to size
+    its slabs from the queries for the step to come out right. Same bounds as that test."""
+    prev = K.set_option("HALO_PERSIST", 0)
+    try:
+        assert K.query("selunet_conv3x3_x2_ok", 32, 32, 64, 64, 64) == 0
+        step_against_oracle("RGB", 2, 32, 32, True, L.seeded_params(3, "RGB", True))
+    finally:
+        K.set_option("HALO_PERSIST", prev)
+
+
 def drifted_params(input_type, selective, seed=77):
     """A parameter state as training leaves it, from one numpy recipe for the net and the oracle: every BN gamma
     ~ N(0, 1) with 5 % exact zeros, every BN beta ~ N(0, 0.5), every 3x3 conv weight row scaled by 2^U(-6, 6) (the
@@ -345,6 +359,8 @@ _ORACLE_CACHE = {}
     ("RGB", 2, 32, 32, True),
     ("RGB", 2, 40, 56, True),    # pyramid 40x56, 20x28, 10x14, 5x7: split-fp16 eligibility flips, ragged tiles
     ("RGB", 3, 24, 24, False),
+    ("RGB", 1, 64, 136, True),   # deepest level 8x17: the odd width puts decoder_layer_4_x's exact-fp32 weight
+                                 # gradient on the fp32 halo kernel's split partials (no Winograd pairs)
 ])
 @pytest.mark.parametrize("x2", ["1", "0"])  # the default split-fp16 path, the exact-fp32 path
 def test_step_against_oracle_drifted_state(input_type, n, h, w, selective, x2, monkeypatch):
