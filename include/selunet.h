@@ -730,6 +730,39 @@ int selunet_patch_auc(const float* out, const float* sel, const float* target,
                       int32_t n, int64_t hw, float t_sel,
                       unsigned long long* rows, void* stream);
 
+/* ---- whole-image prediction I/O --------------------------------------------
+ * A trained network applied to an image of any size: overlapping tiles are gathered from the image, run
+ * through the eval-mode forward, and the tiles' cores (tile minus a halo on every side) stitched into
+ * canvases. origins: DEVICE int32 [n][2] = (y0, x0) of each tile in image coordinates; it is never read on
+ * the host. Both calls: EINVAL for a null pointer, n < 1, H or W outside [1, 65535], th or tw < 8 or not a
+ * multiple of 8. */
+/* img: uint8 [H][W][3] RGB on the device. x: fp32 [n][C][th][tw], C = 3 (mode 0 'RGB', 2 'H_RGB') or 2
+ * (mode 1 'GH'). Element (i, c, y, x) is what selunet_prep_batch_mode gives, without flip, for the source
+ * pixel (refl(y0 + y, H), refl(x0 + x, W)); refl is numpy's 'reflect' padding as an index map: the edge is
+ * not repeated, period 2 (n - 1), folded as often as needed, 0 for n = 1. Origins may be negative or past
+ * the edge. Also EINVAL: a bad mode, x not 16-B aligned. */
+int selunet_tile_gather(const uint8_t* img, int32_t H, int32_t W, const int32_t* origins, int32_t n,
+                        int32_t th, int32_t tw, int32_t mode, float* x, void* stream);
+/* out, sel: fp32 [n][th][tw] logits (sel nullable; sel_plane is null exactly when sel is). The core of
+ * tile i, rows and columns [halo, th - halo) x [halo, tw - halo), goes to canvas position
+ * (y0 + halo, x0 + halo) of the canvases [Hc][Wc] (Hc >= H, Wc >= W, Wc % 8 == 0; the image is their
+ * [:H, :W] corner):
+ *   logit_plane, sel_plane (fp32) = out, sel unchanged;
+ *   mask (uint8) = 127 if sel != NULL and not (sel >= t_sel), else 255 if out >= t_out, else 0
+ *     (a NaN selection abstains, a NaN output is background: the rule of selunet_seg_metrics);
+ *   prob8 (uint8, nullable) = floor(255 sigmoid(out) + 0.5), 0 for a NaN.
+ * counts: uint64 [4], caller-zeroed, += {background, tumor, abstained, pixels} over the canvas pixels with
+ * y < H and x < W. Integer atomics only: the result does not depend on scheduling. Canvas pixels outside
+ * every core of the call are left untouched.
+ * The caller's duty (the origins live on the device): every core lies inside the canvas at a column that
+ * is a multiple of 8. An 8-pixel group that does not is skipped, neither stored nor counted.
+ * Also EINVAL: halo < 0, halo % 8 != 0 or 2 * halo >= min(th, tw); Hc < H, Wc < W or Wc % 8 != 0; out, sel
+ * or a plane not 16-B aligned; counts not 8-B aligned; 2^32 or more core pixels in one call. */
+int selunet_tile_stitch(const float* out, const float* sel, const int32_t* origins, int32_t n, int32_t th,
+                        int32_t tw, int32_t halo, int32_t H, int32_t W, int32_t Hc, int32_t Wc,
+                        float t_out, float t_sel, float* logit_plane, float* sel_plane, uint8_t* mask,
+                        uint8_t* prob8, unsigned long long* counts, void* stream);
+
 /* ---- multi-GPU overlap probe (bench/tools only, not on the training path) ------
  * Stand-in for one bucketed RCCL all-reduce kernel on a single GPU: n_wg workgroups of 256 threads
  * reduce-copy dst[i] += src[i] over their slices of [0, n) (n % 4 == 0, 16-B aligned), repeatedly,

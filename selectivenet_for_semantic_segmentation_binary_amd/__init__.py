@@ -12,6 +12,7 @@ Drop-in replacements for the reference's hot path (yellofi/SelectiveNet_for_sema
 * `SelectiveSweep`                       risk-coverage sweep of eval.py's --s_cut_off in one pass
 * `PatchReport`                          per-patch counts, get_performance metrics and exact ROC AUC
                                         <- utils/compute_metric.py:93-148 (unused there)
+* `predict_image`, `TilePlan`             whole-image prediction: tiles gathered and stitched on the device
 * `parallel.init_data_parallel`        <- torch.nn.DataParallel (train.py:131-134)
 
 All compute runs in libselunet.so (HIP, gfx950); there is no CPU fallback.
@@ -20,6 +21,7 @@ from .layout import count_params, state_dict_keys  # noqa: F401
 from .metrics import PatchReport, SelectiveSweep  # noqa: F401
 from .model import CBR_2D, UNet, UNet_B  # noqa: F401
 from .optim import Adam  # noqa: F401
+from .predict import TilePlan, predict_image  # noqa: F401
 from .selective_loss import (BCEWithLogitsLoss, CrossEntropyLoss, calc_selective_risk_image,  # noqa: F401
                              calc_selective_risk_image_b)
 from . import parallel  # noqa: F401

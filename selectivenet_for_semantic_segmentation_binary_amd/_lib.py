@@ -199,6 +199,9 @@ SIGNATURES = {
     "selunet_seg_metrics_sweep": (c_int32, [P, P, P, c_int64, c_float, P, c_int32, P, P]),
     "selunet_seg_metrics_rows": (c_int32, [P, P, P, c_int32, c_int64, c_float, c_float, P, P]),
     "selunet_patch_auc": (c_int32, [P, P, P, c_int32, c_int64, c_float, P, P]),
+    "selunet_tile_gather": (c_int32, [P, c_int32, c_int32, P, c_int32, c_int32, c_int32, c_int32, P, P]),
+    "selunet_tile_stitch": (c_int32, [P, P, P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                      c_float, c_float, P, P, P, P, P, P]),
     "selunet_set_option": (c_int64, [c_int32, c_int64]),
     "selunet_cu_hold": (c_int32, [P, P, c_int64, c_int32, c_float, P]),
 }

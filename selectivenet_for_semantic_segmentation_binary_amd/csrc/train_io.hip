@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "prep_pixel.h"
 
 namespace selunet {
 
@@ -28,18 +29,7 @@ constexpr int IO_TPB = 256;
 // One thread per (image, row, 4-pixel group): reads 12 B of RGB + 4 B of label (the whole
 // 4-pixel group), writes 3 x 16 B of NCHW planes + 16 B of target. Flips are applied on the
 // READ side (output pixel (y, x) reads source (y', x')), so the stores stay contiguous.
-// CIN = 2: input_type 'GH' (utils/data_utils.py:13-27, applied before Normalization at :223-224):
-// channel 0 = cv2 RGB2GRAY of the [0,1] fp32 image (0.299 R + 0.587 G + 0.114 B), channel 1 = the
-// hematoxylin stain of skimage.color.separate_stains(rgb, hed_from_rgb) (stains = (log(max(rgb,
-// 1e-6)) / log(1e-6)) @ hed_from_rgb, clamped at 0; column 0 of inv(rgb_from_hed)) min-max
-// normalised with the reference's constants -0.66781543 / 1.87798274.
-constexpr double HED_H0 = 1.8779827368521353, HED_H1 = -0.06590806222356332, HED_H2 = -0.6019073634392891;
-constexpr double GH_HMIN = -0.66781543, GH_HMAX = 1.87798274;
-
-// HRGB (CIN = 3): input_type 'H_RGB' (utils/data_utils.py:29-41): the hematoxylin stain h of
-// separate_stains as above, recombined alone by skimage.color.combine_stains(stack(h, 0, 0),
-// rgb_from_hed) = clip(exp(-h * (-log 1e-6) * rgb_from_hed[0]), 0, 1), rgb_from_hed[0] =
-// (0.65, 0.70, 0.29).
+// The per-pixel conversion (CIN = 2: input_type 'GH'; HRGB: 'H_RGB') is prep_pixel (prep_pixel.h).
 template <int CIN, bool HRGB = false>
 __global__ void prep_batch_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ lab,
                                   const uint8_t* __restrict__ flips, int n, int h, int w, float* __restrict__ x,
@@ -61,38 +51,10 @@ __global__ void prep_batch_kernel(const uint8_t* __restrict__ img, const uint8_t
       const int xo = xq * 4 + j;
       const int xs = (f & 1) ? w - 1 - xo : xo;  // np.fliplr (utils/data_utils.py:113-116)
       const uint8_t* p = img + (src_row + xs) * 3;
-      // input/255.0 in float64, astype(float32) (utils/data_utils.py:220-221)
-      float v[3];
+      float v[CIN];
+      prep_pixel<CIN, HRGB>(p[0], p[1], p[2], v);
 #pragma unroll
-      for (int c = 0; c < 3; ++c) v[c] = (float)((double)p[c] / 255.0);
-      if constexpr (HRGB) {
-        const float la = logf(1e-6f);
-        double st = 0.0;
-        st += (double)(logf(fmaxf(v[0], 1e-6f)) / la) * HED_H0;
-        st += (double)(logf(fmaxf(v[1], 1e-6f)) / la) * HED_H1;
-        st += (double)(logf(fmaxf(v[2], 1e-6f)) / la) * HED_H2;
-        const double h = fmax(st, 0.0) * -log(1e-6);
-        const double rf[3] = {0.65, 0.70, 0.29};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float o = (float)fmin(fmax(exp(-h * rf[c]), 0.0), 1.0);
-          xv[c][j] = (o - 0.5f) / 0.5f;
-        }
-      } else if constexpr (CIN == 3) {
-        // (x - 0.5) / 0.5 in float32 (Normalization, utils/data_utils.py:101)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) xv[c][j] = (v[c] - 0.5f) / 0.5f;
-      } else {
-        const float gray = v[0] * 0.299f + v[1] * 0.587f + v[2] * 0.114f;
-        const float la = logf(1e-6f);
-        double st = 0.0;
-        st += (double)(logf(fmaxf(v[0], 1e-6f)) / la) * HED_H0;
-        st += (double)(logf(fmaxf(v[1], 1e-6f)) / la) * HED_H1;
-        st += (double)(logf(fmaxf(v[2], 1e-6f)) / la) * HED_H2;
-        const float hn = (float)((fmax(st, 0.0) - GH_HMIN) / (GH_HMAX - GH_HMIN));
-        xv[0][j] = (gray - 0.5f) / 0.5f;
-        xv[1][j] = (hn - 0.5f) / 0.5f;
-      }
+      for (int c = 0; c < CIN; ++c) xv[c][j] = v[c];
       // (label/255.0).astype(uint8): truncation, so only 255 -> 1
       tv[j] = (float)(uint8_t)((double)lab[src_row + xs] / 255.0);
     }

@@ -1,0 +1,334 @@
+"""Whole-image prediction (MI355X path only; the reference has no such tool: its eval.py keeps
+`make_heatmap` with the saving code commented out): a trained UNet_B applied to an RGB image of any size,
+unlabelled, giving a tumor / abstained / background mask, a probability map and the logit planes.
+
+    python -m selectivenet_for_semantic_segmentation_binary_amd.predict --input slide_region.png more/ \\
+        --model_dir /model/1-fold/checkpoint --model_arch UNet_B --selective 1 --save_dir ./output
+
+The network is fully convolutional in eval mode (BatchNorm uses its running statistics), so the image is
+cut into overlapping tiles (`TilePlan`): each tile is gathered from the uint8 image on the device, the image
+continued past its edges by reflection (`selunet_tile_gather`), run through the forward, and its core — the
+tile minus a halo on every side — stitched into the canvases (`selunet_tile_stitch`). An output pixel
+depends on input pixels at most 51 away, so with a halo of at least HALO_MIN = 56 that is a
+multiple of 8 (the three 2x2 poolings see every tile on the grid of the whole image) the stitched planes are
+those of one forward of the whole reflect-padded image. The image is uploaded once, and nothing is read
+back before the end.
+
+Per input the CLI writes `<stem>_mask.png` (L: 0 background, 127 abstained, 255 tumor), `<stem>_prob.png`
+(L: round(255 sigmoid(logit))) and, with a selective network, `<stem>_select.png` (L: 255 where selected),
+and for the run `predict.json`: per image its size, the tile grid, the pixel counts, the tumor fraction of
+the selected pixels and the coverage. Thresholds are `metrics.logit_threshold(rule="eval")`, as eval's.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib as K
+from . import metrics as MT
+from .data import _CIN, _MODE
+
+HALO_MIN = 56   # the receptive field reaches 51 pixels to either side; the next multiple of 8
+TILE_MAX = 512  # the largest forward the engine is tested at is 512 x 512
+IMAGE_MAX = 65535
+IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".tif", ".tiff", ".bmp")
+COUNT_NAMES = ("background", "tumor", "abstained", "pixels")
+
+
+class TilePlan:
+    """The tiling of an H x W image: square tiles of `tile` pixels whose cores of `core = tile - 2 halo`
+    pixels cover the canvas `Hc x Wc = grid * core >= H x W` exactly once. `origins` (int32 [n][2], row-major
+    over the grid) holds each tile's (y0, x0) = (i core - halo, j core - halo) in image coordinates: negative
+    in the first row and column, and the last ones reach past the image."""
+
+    def __init__(self, H: int, W: int, tile: int = 512, halo: int = HALO_MIN, allow_small_halo: bool = False):
+        H, W, tile, halo = int(H), int(W), int(tile), int(halo)
+        if not (1 <= H <= IMAGE_MAX and 1 <= W <= IMAGE_MAX):
+            raise ValueError(f"TilePlan: image height and width must be in [1, {IMAGE_MAX}] (got {H} x {W})")
+        if halo < 0 or halo % 8 != 0:
+            raise ValueError(f"TilePlan: halo {halo} must be a multiple of 8 (the poolings of every tile must lie on "
+                             "the grid of the whole image)")
+        if halo < HALO_MIN and not allow_small_halo:
+            raise ValueError(f"TilePlan: halo {halo} is below HALO_MIN = {HALO_MIN}: an output pixel sees input up to "
+                             "51 pixels away, so the stitched result would depend on the tiling")
+        if tile % 8 != 0:
+            raise ValueError(f"TilePlan: tile {tile} must be a multiple of 8")
+        if tile <= 2 * halo:
+            raise ValueError(f"TilePlan: tile {tile} leaves no core inside a halo of {halo} (tile must exceed 2 halo)")
+        if tile > TILE_MAX:
+            raise ValueError(f"TilePlan: tile {tile} is above {TILE_MAX}: the engine has no fixture above "
+                             f"{TILE_MAX} x {TILE_MAX}, so larger forwards are untested")
+        self.H, self.W, self.tile, self.halo = H, W, tile, halo
+        self.core = tile - 2 * halo
+        self.grid = (-(-H // self.core), -(-W // self.core))
+        self.Hc, self.Wc = self.grid[0] * self.core, self.grid[1] * self.core
+        ij = np.indices(self.grid).reshape(2, -1).T  # row-major (i, j)
+        self.origins = np.ascontiguousarray(ij * self.core - halo, dtype=np.int32)
+
+    @property
+    def n(self) -> int:
+        return len(self.origins)
+
+    def __repr__(self):
+        return (f"TilePlan({self.H} x {self.W}: {self.grid[0]} x {self.grid[1]} tiles of {self.tile}, halo "
+                f"{self.halo}, canvas {self.Hc} x {self.Wc})")
+
+
+def _check(name, t, dtype):
+    if t is not None and (not torch.is_tensor(t) or t.device.type != "cuda" or t.dtype != dtype
+                          or not t.is_contiguous()):
+        raise RuntimeError(f"{name} must be a contiguous cuda {dtype} tensor")
+
+
+def tile_gather(image_u8: torch.Tensor, origins: torch.Tensor, th: int, tw: int, input_type: str = "RGB",
+                out: torch.Tensor | None = None) -> torch.Tensor:
+    """`selunet_tile_gather`: image uint8 [H,W,3] and origins int32 [n,2], both on the GPU -> x fp32
+    [n,C,th,tw] (into `out` when given)."""
+    if input_type not in _MODE:
+        raise ValueError(f"input_type {input_type!r}: 'RGB', 'GH' or 'H_RGB'")
+    _check("tile_gather: image", image_u8, torch.uint8)
+    _check("tile_gather: origins", origins, torch.int32)
+    if image_u8.dim() != 3 or image_u8.shape[2] != 3:
+        raise ValueError(f"tile_gather: image must be RGB [H,W,3] uint8 (got {tuple(image_u8.shape)})")
+    if origins.dim() != 2 or origins.shape[1] != 2:
+        raise ValueError(f"tile_gather: origins must be [n,2] (got {tuple(origins.shape)})")
+    n, shape = origins.shape[0], (origins.shape[0], _CIN[input_type], th, tw)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=image_u8.device)
+    _check("tile_gather: out", out, torch.float32)
+    if tuple(out.shape) != shape:
+        raise ValueError(f"tile_gather: out must be {shape} (got {tuple(out.shape)})")
+    K.call("selunet_tile_gather", K.ptr(image_u8), image_u8.shape[0], image_u8.shape[1], K.ptr(origins), n, th, tw,
+           _MODE[input_type], K.ptr(out), K.stream_ptr())
+    return out
+
+
+def tile_stitch(out: torch.Tensor, sel: torch.Tensor | None, origins_host: np.ndarray, origins: torch.Tensor,
+                halo: int, H: int, W: int, t_out: float, t_sel: float, logit_plane: torch.Tensor,
+                sel_plane: torch.Tensor | None, mask: torch.Tensor, prob8: torch.Tensor | None,
+                counts: torch.Tensor):
+    """`selunet_tile_stitch`: the cores of the output tiles out / sel [n,th,tw] into the canvases [Hc,Wc].
+    `origins_host` is the host copy of the device `origins`: the library never reads the device array on the
+    host, so the rule it cannot check — every core inside the canvas, at a column that is a multiple of 8 — is
+    checked here."""
+    _check("tile_stitch: out", out, torch.float32)
+    _check("tile_stitch: sel", sel, torch.float32)
+    _check("tile_stitch: origins", origins, torch.int32)
+    _check("tile_stitch: logit_plane", logit_plane, torch.float32)
+    _check("tile_stitch: sel_plane", sel_plane, torch.float32)
+    _check("tile_stitch: mask", mask, torch.uint8)
+    _check("tile_stitch: prob8", prob8, torch.uint8)
+    _check("tile_stitch: counts", counts, torch.int64)
+    if out.dim() != 3 or (sel is not None and sel.shape != out.shape):
+        raise ValueError("tile_stitch: out and sel must be [n,th,tw] of one shape")
+    n, th, tw = out.shape
+    oh = np.asarray(origins_host)
+    if oh.shape != (n, 2) or tuple(origins.shape) != (n, 2):
+        raise ValueError(f"tile_stitch: origins must be [{n},2] on the host and on the device")
+    if logit_plane.dim() != 2 or counts.numel() != 4:
+        raise ValueError("tile_stitch: logit_plane must be [Hc,Wc] and counts hold 4 words")
+    Hc, Wc = logit_plane.shape
+    for name, t in (("sel_plane", sel_plane), ("mask", mask), ("prob8", prob8)):
+        if t is not None and tuple(t.shape) != (Hc, Wc):
+            raise ValueError(f"tile_stitch: {name} must be [{Hc},{Wc}] like logit_plane (got {tuple(t.shape)})")
+    cy, cx = oh[:, 0].astype(np.int64) + halo, oh[:, 1].astype(np.int64) + halo
+    if 0 <= 2 * halo < min(th, tw) and (
+            (cy < 0).any() or (cx < 0).any() or (cy + th - 2 * halo > Hc).any() or (cx + tw - 2 * halo > Wc).any()
+            or (cx % 8 != 0).any()):
+        raise K.SelunetError(f"selunet_tile_stitch: a tile's core does not lie inside the {Hc} x {Wc} canvas at a "
+                             "column that is a multiple of 8")
+    K.call("selunet_tile_stitch", K.ptr(out), K.ptr(sel), K.ptr(origins), n, th, tw, halo, H, W, Hc, Wc, t_out, t_sel,
+           K.ptr(logit_plane), K.ptr(sel_plane), K.ptr(mask), K.ptr(prob8), K.ptr(counts), K.stream_ptr())
+
+
+@dataclass
+class Prediction:
+    """`predict_image`'s result. logit, selection (None for a non-selective network), mask, prob8 (None when
+    not asked for): device tensors [H,W], views of the canvases; counts: int64 numpy {background, tumor,
+    abstained, pixels} over the image; plan: the tiling used."""
+    logit: torch.Tensor
+    selection: torch.Tensor | None
+    mask: torch.Tensor
+    prob8: torch.Tensor | None
+    counts: np.ndarray
+    plan: TilePlan
+
+    @property
+    def coverage(self) -> float:
+        """The share of the image's pixels that were not abstained on."""
+        return float(self.counts[0] + self.counts[1]) / float(self.counts[3])
+
+    @property
+    def tumor_fraction(self) -> float:
+        """The share of tumor among the selected pixels (NaN when none is selected)."""
+        sel = int(self.counts[0] + self.counts[1])
+        return float(self.counts[1]) / sel if sel else float("nan")
+
+
+def predict_image(net, image_u8, *, tile: int = 512, halo: int = HALO_MIN, batch_size: int = 16,
+                  cut_off: float = 0.5, s_cut_off: float = 0.5, single_scale: str = "sigmoid",
+                  input_type: str = "RGB", prob8: bool = True, allow_small_halo: bool = False) -> Prediction:
+    """Apply `net` (a UNet_B on a cuda device, in eval mode) to `image_u8`, a numpy or torch uint8 [H,W,3] RGB
+    image of any size: gather -> net -> stitch per batch of `batch_size` tiles, on the current stream."""
+    if net.training:
+        raise RuntimeError("predict_image needs the network in eval mode (net.eval()): tiling is exact only with "
+                           "the running BatchNorm statistics")
+    if batch_size < 1:
+        raise ValueError(f"predict_image: batch_size {batch_size} must be >= 1")
+    device = next(net.parameters()).device
+    if device.type != "cuda":
+        raise RuntimeError("predict_image runs on the GPU only (no CPU fallback); move the network to a cuda device")
+    img = image_u8 if torch.is_tensor(image_u8) else torch.from_numpy(np.ascontiguousarray(image_u8))
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+        raise ValueError(f"predict_image: the image must be uint8 [H,W,3] RGB (got {img.dtype} {tuple(img.shape)})")
+    H, W = int(img.shape[0]), int(img.shape[1])
+    plan = TilePlan(H, W, tile, halo, allow_small_halo)
+    t_out = MT.logit_threshold("eval", cut_off, single_scale)
+    t_sel = MT.logit_threshold("eval", s_cut_off, single_scale)
+    selective = bool(net.selective)
+    with torch.cuda.device(device), torch.no_grad():
+        img = img.to(device).contiguous()  # the one upload
+        origins = torch.from_numpy(plan.origins).to(device)
+        # the cores cover the canvases exactly once: no initial value is read
+        logit = torch.empty(plan.Hc, plan.Wc, dtype=torch.float32, device=device)
+        selection = torch.empty_like(logit) if selective else None
+        mask = torch.empty(plan.Hc, plan.Wc, dtype=torch.uint8, device=device)
+        prob = torch.empty_like(mask) if prob8 else None
+        counts = torch.zeros(4, dtype=torch.int64, device=device)  # uint64 bits
+        x_buf = torch.empty(min(batch_size, plan.n), _CIN[input_type], tile, tile, dtype=torch.float32, device=device)
+        for a in range(0, plan.n, batch_size):
+            b = min(a + batch_size, plan.n)  # the last batch is run as ragged as it is
+            x = tile_gather(img, origins[a:b], tile, tile, input_type, out=x_buf[:b - a])
+            res = net(x)
+            out, sel = (res[0], res[1]) if selective else (res, None)
+            tile_stitch(out.contiguous(), None if sel is None else sel.contiguous(), plan.origins[a:b], origins[a:b],
+                        halo, H, W, t_out, t_sel, logit, selection, mask, prob, counts)
+        host_counts = counts.cpu().numpy().astype(np.int64)  # the one read
+    return Prediction(logit[:H, :W], None if selection is None else selection[:H, :W], mask[:H, :W],
+                      None if prob is None else prob[:H, :W], host_counts, plan)
+
+
+# ----------------------------------------------------------------------------- CLI
+def parse_arguments(argv=None):
+    parser = argparse.ArgumentParser(description="whole-image prediction with a trained UNet_B")
+    parser.add_argument('--input', type=str, nargs='+', required=True, help='image files or directories of images')
+    parser.add_argument('--model_dir', type=str, required=True, help='directory holding exactly one .pth checkpoint')
+    # ---- as eval's
+    parser.add_argument('--model_arch', type=str, default='UNet_B', choices=['UNet_B'])
+    parser.add_argument('--selective', type=bool, default=False, help='Is the network based on SelectiveNet?')
+    parser.add_argument('--input_type', type=str, default='RGB')
+    parser.add_argument('--cut_off', type=float, default=0.5, help='prob > cut_off -> pred: 1')
+    parser.add_argument('--s_cut_off', type=float, default=0.5, help='selection > cut_off -> select: 1')
+    parser.add_argument('--single_scale', type=str, default='sigmoid', choices=['None', 'clip', 'sigmoid', 'minmax'])
+    parser.add_argument('--batch_size', type=int, default=16, help='tiles per forward')
+    parser.add_argument('--local_rank', type=int, nargs='+', default=[0], help='local gpu ids (the first is used)')
+    parser.add_argument('--save_dir', type=str, default='./output', help='saving results')
+    parser.add_argument('--compute_dtype', type=str, default='fp32', choices=['fp32', 'bf16'])
+    parser.add_argument('--fp32_path', type=str, default='exact', choices=['exact', 'split'],
+                        help='conv kernels of the fp32 forward: exact fp32, or the split-fp16 kernels of training')
+    # ---- tiling
+    parser.add_argument('--tile', type=int, default=TILE_MAX, help='tile side, a multiple of 8, at most 512')
+    parser.add_argument('--halo', type=int, default=HALO_MIN, help='halo, a multiple of 8, at least 56')
+    args = parser.parse_args(argv)
+    if args.fp32_path == 'split' and args.compute_dtype == 'bf16':
+        parser.error('--fp32_path split is an fp32 path: not with --compute_dtype bf16')
+    return args
+
+
+def list_inputs(inputs) -> list:
+    """The image files named by --input, directories expanded (sorted, by extension); every stem once."""
+    files = []
+    for p in inputs:
+        if os.path.isdir(p):
+            found = sorted(f for f in os.listdir(p) if f.lower().endswith(IMAGE_EXTENSIONS))
+            if not found:
+                raise FileNotFoundError(f"no image files in {p}")
+            files += [os.path.join(p, f) for f in found]
+        elif os.path.isfile(p):
+            files.append(p)
+        else:
+            raise FileNotFoundError(f"--input {p}: no such file or directory")
+    stems = [os.path.splitext(os.path.basename(f))[0] for f in files]
+    twice = sorted({s for s in stems if stems.count(s) > 1})
+    if twice:
+        raise ValueError(f"inputs share the stems {twice}: their outputs would overwrite each other")
+    return files
+
+
+def find_checkpoint(model_dir) -> str:
+    names = sorted(c for c in os.listdir(model_dir) if c.endswith('.pth'))
+    if not names:
+        raise FileNotFoundError(f"no .pth checkpoint in {model_dir}")
+    if len(names) > 1:
+        raise ValueError(f"{model_dir} holds {len(names)} checkpoints ({', '.join(names)}): predict applies one "
+                         "network; ensembles are eval's business")
+    return os.path.join(model_dir, names[0])
+
+
+def image_record(path, pred: Prediction) -> dict:
+    """One image's entry of predict.json."""
+    c = [int(v) for v in pred.counts]
+    sel = c[0] + c[1]
+    return {"input": path, "height": pred.plan.H, "width": pred.plan.W, "tile": pred.plan.tile,
+            "halo": pred.plan.halo, "grid": list(pred.plan.grid), "tiles": pred.plan.n,
+            "counts": dict(zip(COUNT_NAMES, c)),
+            "tumor_fraction_of_selected": c[1] / sel if sel else None,
+            "coverage": sel / c[3]}
+
+
+def predict_files(args) -> dict:
+    from PIL import Image
+
+    import selectivenet_for_semantic_segmentation_binary_amd as S
+    from . import net_utils
+
+    if args.input_type not in _MODE:
+        raise ValueError(f"input_type {args.input_type!r}: 'RGB', 'GH' or 'H_RGB' (utils/data_utils.py:223-226)")
+    files = list_inputs(args.input)
+    ckpt = find_checkpoint(args.model_dir)
+    TilePlan(8, 8, args.tile, args.halo)  # the tiling arguments, before anything is loaded
+    device = torch.device("cuda", args.local_rank[0])
+    torch.cuda.set_device(device)
+    dt = torch.bfloat16 if args.compute_dtype == 'bf16' else torch.float32
+    net = S.UNet_B(args.input_type, selective=args.selective, compute_dtype=dt, fp32_eval_path=args.fp32_path)
+    net_utils.net_test_load(ckpt, net)
+    net = net.to(device).train(False)
+    os.makedirs(args.save_dir, exist_ok=True)
+    doc = {"checkpoint": ckpt, "selective": bool(args.selective), "input_type": args.input_type,
+           "cut_off": args.cut_off, "s_cut_off": args.s_cut_off, "single_scale": args.single_scale, "images": []}
+    for path in files:
+        image = np.array(Image.open(path).convert("RGB"))
+        pred = predict_image(net, image, tile=args.tile, halo=args.halo, batch_size=args.batch_size,
+                             cut_off=args.cut_off, s_cut_off=args.s_cut_off, single_scale=args.single_scale,
+                             input_type=args.input_type)
+        stem = os.path.join(args.save_dir, os.path.splitext(os.path.basename(path))[0])
+        mask = pred.mask.cpu().numpy()
+        Image.fromarray(mask).save(stem + "_mask.png")
+        Image.fromarray(pred.prob8.cpu().numpy()).save(stem + "_prob.png")
+        if args.selective:
+            Image.fromarray(np.where(mask != 127, 255, 0).astype(np.uint8)).save(stem + "_select.png")
+        rec = image_record(path, pred)
+        doc["images"].append(rec)
+        c = rec["counts"]
+        print(f'    {path}: {rec["height"]} x {rec["width"]}, {rec["grid"][0]} x {rec["grid"][1]} tiles, tumor '
+              f'{c["tumor"]} background {c["background"]} abstained {c["abstained"]} (coverage {rec["coverage"]:.4f})')
+    with open(os.path.join(args.save_dir, "predict.json"), "w") as fh:
+        json.dump(doc, fh, indent=1)
+    return doc
+
+
+def main(argv=None):
+    args = parse_arguments(sys.argv[1:] if argv is None else argv)
+    print('\nargs={}\n'.format(args))
+    predict_files(args)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
