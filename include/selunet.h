@@ -763,6 +763,51 @@ int selunet_tile_stitch(const float* out, const float* sel, const int32_t* origi
                         float t_out, float t_sel, float* logit_plane, float* sel_plane, uint8_t* mask,
                         uint8_t* prob8, unsigned long long* counts, void* stream);
 
+/* ---- flip / D4 test-time augmentation of whole-image prediction --------------
+ * Member k = 0..7 of the ensemble is the prediction of T_k(image) mapped back by T_k^-1: bit 2 of k
+ * transposes the image, then bit 1 flips its rows, then bit 0 its columns. The image is transposed once
+ * (selunet_image_transpose), so the per-tile calls take a flip code 0..3 (k & 3) and the image of the
+ * member's orientation class: the image itself (k < 4) or its transpose. */
+/* selunet_tile_gather of the flipped image without forming it: element (i, c, y, x) comes from source row
+ * fy(refl(y0 + y, H)) and column fx(refl(x0 + x, W)), fy(r) = H - 1 - r if flip & 2 else r, fx(c) = W - 1 - c if
+ * flip & 1 else c. Arguments and EINVALs as selunet_tile_gather's; also EINVAL: flip outside [0, 3]. */
+int selunet_tile_gather_flip(const uint8_t* img, int32_t H, int32_t W, const int32_t* origins, int32_t n,
+                             int32_t th, int32_t tw, int32_t mode, int32_t flip, float* x, void* stream);
+/* src: uint8 [H][W][3] -> dst: uint8 [W][H][3], dst[x][y] = src[y][x]; not in place. EINVAL: a null
+ * pointer, src == dst, H or W outside [1, 65535]. */
+int selunet_image_transpose(const uint8_t* src, int32_t H, int32_t W, uint8_t* dst, void* stream);
+/* One batch of one member's output tiles into the running sums of its orientation class. out, sel: fp32
+ * [n][th][tw] as selunet_tile_stitch's (sel, sum_sel and sel_votes all null or all given); H x W: the
+ * member's image (the transposed size for k >= 4). Canvas pixel (cy, cx) of a core with cy < H and cx < W goes
+ * to (fy(cy), fx(cx)) of the planes [H][ws] (ws >= W, ws % 8 == 0):
+ *   sum_out, sum_sel (fp32) += out, sel       (first = 1: = out, sel; the class's first member);
+ *   votes, sel_votes (uint8) += out >= t_out, sel >= t_sel   (first = 1: =; a NaN casts no vote).
+ * Everything else in the planes is left untouched. Each pixel is read and written by one thread, without
+ * atomics: with one call after another on one stream the order of the additions is the order of the calls.
+ * The caller's duty: the cores of one call do not overlap, and a member's calls cover every image pixel once.
+ * Also EINVAL: the halo rule of selunet_tile_stitch; flip outside [0, 3]; first not 0 or 1; ws < W or
+ * ws % 8 != 0; tiles or planes not 16-B aligned. */
+int selunet_tta_accumulate(const float* out, const float* sel, const int32_t* origins, int32_t n, int32_t th,
+                           int32_t tw, int32_t halo, int32_t flip, int32_t first, int32_t H, int32_t W,
+                           int32_t ws, float t_out, float t_sel, float* sum_out, float* sum_sel,
+                           uint8_t* votes, uint8_t* sel_votes, void* stream);
+/* The mean of the members and what follows from it. a_*: the sums and votes of members 0..3, [H][wa]; b_*:
+ * those of members 4..7 in the transposed orientation, [W][hb] (all null for members = 4). For y < H, x < wa
+ * (outputs [H][wa]; wa >= W, hb >= H, both multiples of 8):
+ *   logit_plane, sel_plane = a * 0.25 (members = 4) or (a + b^T) * 0.125 (members = 8), in fp32;
+ *   mask, prob8 (nullable): selunet_tile_stitch's rules applied to those means;
+ *   votes, sel_votes = a_votes (+ b_votes^T), a_sel_votes (+ b_sel_votes^T).
+ * counts: uint64 [4], caller-zeroed, += {background, tumor, abstained, pixels} over x < W, integer atomics.
+ * The selection arguments (a_sel, a_sel_votes, sel_plane, sel_votes, and b_sel, b_sel_votes for members = 8)
+ * are all given or all null. EINVAL: members not 4 or 8; a missing or a superfluous pointer; H or W outside
+ * [1, 65535]; wa < W, hb < H or either not a multiple of 8; a plane not 16-B aligned; counts not 8-B aligned. */
+int selunet_tta_finalize(const float* a_out, const float* a_sel, const uint8_t* a_votes,
+                         const uint8_t* a_sel_votes, const float* b_out, const float* b_sel,
+                         const uint8_t* b_votes, const uint8_t* b_sel_votes, int32_t members, int32_t H,
+                         int32_t W, int32_t wa, int32_t hb, float t_out, float t_sel, float* logit_plane,
+                         float* sel_plane, uint8_t* mask, uint8_t* prob8, uint8_t* votes, uint8_t* sel_votes,
+                         unsigned long long* counts, void* stream);
+
 /* ---- multi-GPU overlap probe (bench/tools only, not on the training path) ------
  * Stand-in for one bucketed RCCL all-reduce kernel on a single GPU: n_wg workgroups of 256 threads
  * reduce-copy dst[i] += src[i] over their slices of [0, n) (n % 4 == 0, 16-B aligned), repeatedly,

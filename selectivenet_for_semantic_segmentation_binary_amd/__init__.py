@@ -12,7 +12,8 @@ Drop-in replacements for the reference's hot path (yellofi/SelectiveNet_for_sema
 * `SelectiveSweep`                       risk-coverage sweep of eval.py's --s_cut_off in one pass
 * `PatchReport`                          per-patch counts, get_performance metrics and exact ROC AUC
                                         <- utils/compute_metric.py:93-148 (unused there)
-* `predict_image`, `TilePlan`             whole-image prediction: tiles gathered and stitched on the device
+* `predict_image`, `TilePlan`             whole-image prediction: tiles gathered and stitched on the device,
+                                        optionally averaged over the image's flips / D4 orientations (tta=)
 * `parallel.init_data_parallel`        <- torch.nn.DataParallel (train.py:131-134)
 
 All compute runs in libselunet.so (HIP, gfx950); there is no CPU fallback.

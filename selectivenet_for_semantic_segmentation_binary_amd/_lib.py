@@ -202,6 +202,10 @@ SIGNATURES = {
     "selunet_tile_gather": (c_int32, [P, c_int32, c_int32, P, c_int32, c_int32, c_int32, c_int32, P, P]),
     "selunet_tile_stitch": (c_int32, [P, P, P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                       c_float, c_float, P, P, P, P, P, P]),
+    "selunet_tile_gather_flip": (c_int32, [P, c_int32, c_int32, P, c_int32, c_int32, c_int32, c_int32, c_int32, P, P]),
+    "selunet_image_transpose": (c_int32, [P, c_int32, c_int32, P, P]),
+    "selunet_tta_accumulate": (c_int32, [P, P, P] + [c_int32] * 9 + [c_float, c_float, P, P, P, P, P]),
+    "selunet_tta_finalize": (c_int32, [P] * 8 + [c_int32] * 5 + [c_float, c_float] + [P] * 8),
     "selunet_set_option": (c_int64, [c_int32, c_int64]),
     "selunet_cu_hold": (c_int32, [P, P, c_int64, c_int32, c_float, P]),
 }

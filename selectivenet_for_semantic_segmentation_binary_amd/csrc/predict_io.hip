@@ -11,26 +11,10 @@
 #include <algorithm>
 
 #include "common.h"
+#include "predict_common.h"
 #include "prep_pixel.h"
 
 namespace selunet {
-
-constexpr int PRED_TPB = 256;
-constexpr int PRED_MAX_HW = 65535;  // image height / width the calls take
-
-// numpy's 'reflect' padding as an index map onto [0, n): the edge is not repeated, period 2 (n - 1),
-// folded as often as needed; 0 for n = 1.
-__device__ __forceinline__ int reflect_index(int64_t i, int n) {
-  if (n == 1) return 0;
-  const int64_t period = 2 * ((int64_t)n - 1);
-  int64_t m = i % period;
-  m = m < 0 ? m + period : m;
-  return (int)(m < n ? m : period - m);
-}
-
-struct rgb4 {
-  uint32_t w[3];
-};
 
 // One thread per (tile, row, 4-pixel group): 12 B of RGB in, CIN x 16 B of NCHW planes out. A group whose
 // four source pixels lie inside the row (no fold) reads them as one 12-B load at whatever byte alignment
@@ -79,14 +63,6 @@ __global__ void tile_gather_kernel(const uint8_t* __restrict__ img, int h, int w
   }
 }
 
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-// floor(255 sigmoid(v) + 0.5) as a byte; NaN -> 0
-__device__ __forceinline__ uint32_t prob_level(float v) {
-  const float p = 255.0f * sigmoidf_(v) + 0.5f;
-  return p >= 0.0f ? (uint32_t)p : 0u;  // p in [0.5, 255.5]: the conversion truncates = floor; NaN fails the test
-}
-
 // One thread per (tile, core row, 8-pixel group): 2 x 16 B of each logit tile in; 2 x 16 B per logit
 // canvas and 8 B per byte canvas out. th, tw, halo and the canvas width are multiples of 8 and so is a
 // core's canvas column (the caller's duty for the origins: a group that is not, or that does not lie
@@ -126,9 +102,8 @@ __global__ __launch_bounds__(PRED_TPB) void tile_stitch_kernel(
     for (int j = 0; j < 8; ++j) {
       const float o = j < 4 ? o0[j & 3] : o1[j & 3];
       const float s = j < 4 ? s0[j & 3] : s1[j & 3];
-      // `not (sel >= t_sel)`: a NaN selection abstains; a NaN output is background (seg_metrics_kernel's rule)
-      const int cls = (sel != nullptr && !(s >= t_sel)) ? 2 : (o >= t_out ? 1 : 0);
-      const uint32_t level = cls == 2 ? 127u : (cls == 1 ? 255u : 0u);
+      const int cls = pixel_class(sel != nullptr, s, o, t_sel, t_out);
+      const uint32_t level = mask_level(cls);
       m[j >> 2] |= level << (8 * (j & 3));
       if (prob8) p[j >> 2] |= prob_level(o) << (8 * (j & 3));
       const bool counted = cy < h && cx + j < w;
@@ -138,36 +113,7 @@ __global__ __launch_bounds__(PRED_TPB) void tile_stitch_kernel(
     *reinterpret_cast<u32x2*>(mask + dst) = m;
     if (prob8) *reinterpret_cast<u32x2*>(prob8 + dst) = p;
   }
-  __shared__ unsigned red[PRED_TPB / 64][3];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    unsigned v = c[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    // words 0..2: the class of this thread; word 3, `pixels`: all three
-    unsigned long long s = 0;
-    for (int wv = 0; wv < PRED_TPB / 64; ++wv)
-      for (int k = 0; k < 3; ++k)
-        if (threadIdx.x == 3 || threadIdx.x == k) s += red[wv][k];
-    if (s) atomicAdd(counts + threadIdx.x, s);
-  }
-}
-
-// The argument rules the two calls share; `fn` names the call in the message.
-static int tile_args(const char* fn, const int32_t* origins, int32_t n, int32_t h, int32_t w, int32_t th, int32_t tw) {
-  SELUNET_REQUIRE(origins, "%s: null origins", fn);
-  SELUNET_REQUIRE(n >= 1, "%s: n must be >= 1 (got %d)", fn, n);
-  SELUNET_REQUIRE(h >= 1 && h <= PRED_MAX_HW && w >= 1 && w <= PRED_MAX_HW,
-                  "%s: image height and width must be in [1, %d] (got %d x %d)", fn, PRED_MAX_HW, h, w);
-  SELUNET_REQUIRE(th >= 8 && tw >= 8 && th % 8 == 0 && tw % 8 == 0,
-                  "%s: tile height and width must be multiples of 8, at least 8 (got %d x %d)", fn, th, tw);
-  SELUNET_REQUIRE(((uintptr_t)origins & 3) == 0, "%s: origins must be 4-B aligned", fn);
-  return SELUNET_OK;
+  add_class_counts(c, counts);
 }
 
 }  // namespace selunet

@@ -1,6 +1,7 @@
 // One RGB uint8 pixel -> the network's input channels: the per-pixel part of PatchDataset.__getitem__'s
 // transforms (utils/data_utils.py:13-41, 94-106, 220-226), shared by selunet_prep_batch (train_io.hip)
-// and selunet_tile_gather (predict_io.hip) so that the two give the same bits for the same pixel.
+// selunet_tile_gather (predict_io.hip) and selunet_tile_gather_flip (predict_tta.hip) so that all of them
+// give the same bits for the same pixel.
 #pragma once
 
 #include "common.h"
@@ -21,8 +22,12 @@ constexpr double GH_HMIN = -0.66781543, GH_HMAX = 1.87798274;
 // (0.65, 0.70, 0.29).
 //
 // r, g, b: the pixel's bytes; o[c]: channel c of the normalised input.
+// No multiply-add of this function is fused: left to the compiler, which products of a sum it fuses depends on
+// the kernel around the call and on the pixel's place in a thread's group of four, so that two kernels — or
+// two columns of one — could differ in the last bit for the same pixel.
 template <int CIN, bool HRGB>
 __device__ __forceinline__ void prep_pixel(unsigned r, unsigned g, unsigned b, float (&o)[CIN]) {
+#pragma clang fp contract(off)
   // input/255.0 in float64, astype(float32) (utils/data_utils.py:220-221)
   const float v[3] = {(float)((double)r / 255.0), (float)((double)g / 255.0), (float)((double)b / 255.0)};
   if constexpr (HRGB) {

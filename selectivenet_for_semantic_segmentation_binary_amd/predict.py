@@ -18,6 +18,11 @@ Per input the CLI writes `<stem>_mask.png` (L: 0 background, 127 abstained, 255 
 (L: round(255 sigmoid(logit))) and, with a selective network, `<stem>_select.png` (L: 255 where selected),
 and for the run `predict.json`: per image its size, the tile grid, the pixel counts, the tumor fraction of
 the selected pixels and the coverage. Thresholds are `metrics.logit_threshold(rule="eval")`, as eval's.
+
+`--tta flips` / `--tta d4` (`predict_image(..., tta=)`) averages the logit planes of the 4 flips / the 8 flips and
+transposes of the image on the device; the mask, the probability map and the counts then come from
+the means, `<stem>_votes.png` (L: votes * 255 // members) shows how many orientations say tumor, and predict.json
+carries "tta" and per image "unanimous_fraction", the share of pixels on which all orientations agree.
 """
 from __future__ import annotations
 
@@ -39,6 +44,7 @@ TILE_MAX = 512  # the largest forward the engine is tested at is 512 x 512
 IMAGE_MAX = 65535
 IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".tif", ".tiff", ".bmp")
 COUNT_NAMES = ("background", "tumor", "abstained", "pixels")
+TTA_MEMBERS = {"none": 1, "flips": 4, "d4": 8}  # members of the test-time-augmentation ensemble
 
 
 class TilePlan:
@@ -137,27 +143,140 @@ def tile_stitch(out: torch.Tensor, sel: torch.Tensor | None, origins_host: np.nd
     for name, t in (("sel_plane", sel_plane), ("mask", mask), ("prob8", prob8)):
         if t is not None and tuple(t.shape) != (Hc, Wc):
             raise ValueError(f"tile_stitch: {name} must be [{Hc},{Wc}] like logit_plane (got {tuple(t.shape)})")
+    _check_cores("tile_stitch", oh, n, th, tw, halo, Hc, Wc)
+    K.call("selunet_tile_stitch", K.ptr(out), K.ptr(sel), K.ptr(origins), n, th, tw, halo, H, W, Hc, Wc, t_out, t_sel,
+           K.ptr(logit_plane), K.ptr(sel_plane), K.ptr(mask), K.ptr(prob8), K.ptr(counts), K.stream_ptr())
+
+
+def _check_cores(fn, origins_host, n, th, tw, halo, Hc, Wc):
+    """The rule the library cannot check (the origins live on the device), on their host copy: every core
+    inside the Hc x Wc canvas at a column that is a multiple of 8."""
+    oh = np.asarray(origins_host)
+    if oh.shape != (n, 2):
+        raise ValueError(f"{fn}: origins must be [{n},2] on the host and on the device")
     cy, cx = oh[:, 0].astype(np.int64) + halo, oh[:, 1].astype(np.int64) + halo
     if 0 <= 2 * halo < min(th, tw) and (
             (cy < 0).any() or (cx < 0).any() or (cy + th - 2 * halo > Hc).any() or (cx + tw - 2 * halo > Wc).any()
             or (cx % 8 != 0).any()):
-        raise K.SelunetError(f"selunet_tile_stitch: a tile's core does not lie inside the {Hc} x {Wc} canvas at a "
+        raise K.SelunetError(f"selunet_{fn}: a tile's core does not lie inside the {Hc} x {Wc} canvas at a "
                              "column that is a multiple of 8")
-    K.call("selunet_tile_stitch", K.ptr(out), K.ptr(sel), K.ptr(origins), n, th, tw, halo, H, W, Hc, Wc, t_out, t_sel,
-           K.ptr(logit_plane), K.ptr(sel_plane), K.ptr(mask), K.ptr(prob8), K.ptr(counts), K.stream_ptr())
+
+
+def tile_gather_flip(image_u8: torch.Tensor, origins: torch.Tensor, th: int, tw: int, input_type: str = "RGB",
+                     flip: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """`selunet_tile_gather_flip`: `tile_gather` of the image with its rows (flip & 2) and columns (flip & 1)
+    reversed, without forming that image."""
+    if input_type not in _MODE:
+        raise ValueError(f"input_type {input_type!r}: 'RGB', 'GH' or 'H_RGB'")
+    _check("tile_gather_flip: image", image_u8, torch.uint8)
+    _check("tile_gather_flip: origins", origins, torch.int32)
+    if image_u8.dim() != 3 or image_u8.shape[2] != 3:
+        raise ValueError(f"tile_gather_flip: image must be RGB [H,W,3] uint8 (got {tuple(image_u8.shape)})")
+    if origins.dim() != 2 or origins.shape[1] != 2:
+        raise ValueError(f"tile_gather_flip: origins must be [n,2] (got {tuple(origins.shape)})")
+    n, shape = origins.shape[0], (origins.shape[0], _CIN[input_type], th, tw)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=image_u8.device)
+    _check("tile_gather_flip: out", out, torch.float32)
+    if tuple(out.shape) != shape:
+        raise ValueError(f"tile_gather_flip: out must be {shape} (got {tuple(out.shape)})")
+    K.call("selunet_tile_gather_flip", K.ptr(image_u8), image_u8.shape[0], image_u8.shape[1], K.ptr(origins), n, th,
+           tw, _MODE[input_type], int(flip), K.ptr(out), K.stream_ptr())
+    return out
+
+
+def image_transpose(image_u8: torch.Tensor) -> torch.Tensor:
+    """`selunet_image_transpose`: uint8 [H,W,3] on the GPU -> a new [W,H,3]."""
+    _check("image_transpose: image", image_u8, torch.uint8)
+    if image_u8.dim() != 3 or image_u8.shape[2] != 3:
+        raise ValueError(f"image_transpose: image must be RGB [H,W,3] uint8 (got {tuple(image_u8.shape)})")
+    H, W = image_u8.shape[:2]
+    out = torch.empty(W, H, 3, dtype=torch.uint8, device=image_u8.device)
+    K.call("selunet_image_transpose", K.ptr(image_u8), H, W, K.ptr(out), K.stream_ptr())
+    return out
+
+
+def tta_accumulate(out: torch.Tensor, sel: torch.Tensor | None, origins_host: np.ndarray, origins: torch.Tensor,
+                   halo: int, flip: int, first: bool, H: int, W: int, Hc: int, Wc: int, t_out: float, t_sel: float,
+                   sum_out: torch.Tensor, sum_sel: torch.Tensor | None, votes: torch.Tensor,
+                   sel_votes: torch.Tensor | None):
+    """`selunet_tta_accumulate`: the cores of one member's output tiles out / sel [n,th,tw], flipped back by
+    `flip`, into the sums and votes [H,ws] of the member's orientation class (`first`: stored, not added).
+    H x W is the member's image and Hc x Wc its plan's canvas; `origins_host` as `tile_stitch`'s."""
+    _check("tta_accumulate: out", out, torch.float32)
+    _check("tta_accumulate: sel", sel, torch.float32)
+    _check("tta_accumulate: origins", origins, torch.int32)
+    _check("tta_accumulate: sum_out", sum_out, torch.float32)
+    _check("tta_accumulate: sum_sel", sum_sel, torch.float32)
+    _check("tta_accumulate: votes", votes, torch.uint8)
+    _check("tta_accumulate: sel_votes", sel_votes, torch.uint8)
+    if out.dim() != 3 or (sel is not None and sel.shape != out.shape):
+        raise ValueError("tta_accumulate: out and sel must be [n,th,tw] of one shape")
+    n, th, tw = out.shape
+    if tuple(origins.shape) != (n, 2):
+        raise ValueError(f"tta_accumulate: origins must be [{n},2] on the host and on the device")
+    if sum_out.dim() != 2 or sum_out.shape[0] < H:
+        raise ValueError(f"tta_accumulate: sum_out must be [>= {H}, ws] (got {tuple(sum_out.shape)})")
+    for name, t in (("sum_sel", sum_sel), ("votes", votes), ("sel_votes", sel_votes)):
+        if t is not None and t.shape != sum_out.shape:
+            raise ValueError(f"tta_accumulate: {name} must be {tuple(sum_out.shape)} like sum_out (got {tuple(t.shape)})")
+    _check_cores("tta_accumulate", origins_host, n, th, tw, halo, Hc, Wc)
+    K.call("selunet_tta_accumulate", K.ptr(out), K.ptr(sel), K.ptr(origins), n, th, tw, halo, int(flip), int(first),
+           H, W, sum_out.shape[1], t_out, t_sel, K.ptr(sum_out), K.ptr(sum_sel), K.ptr(votes), K.ptr(sel_votes),
+           K.stream_ptr())
+
+
+def tta_finalize(a, b, members: int, H: int, W: int, t_out: float, t_sel: float, prob8: bool = True):
+    """`selunet_tta_finalize`. a = (sum_out, sum_sel | None, votes, sel_votes | None), each [H,wa]: the class of
+    members 0..3; b: the same for members 4..7, each [W,hb], or None for 4 members. Returns (logit, selection |
+    None, mask, prob8 | None, votes, sel_votes | None), each [H,wa], and the device counts (int64 [4])."""
+    kinds = (torch.float32, torch.float32, torch.uint8, torch.uint8)
+    for name, group in (("a", a), ("b", b)):
+        for t, dt in zip(group or (), kinds):
+            _check(f"tta_finalize: {name}", t, dt)
+            if t is not None and t.shape != group[0].shape:
+                raise ValueError(f"tta_finalize: the planes of {name} must be of one shape")
+    if a[0].dim() != 2 or a[0].shape[0] < H or (b is not None and (b[0].dim() != 2 or b[0].shape[0] < W)):
+        raise ValueError("tta_finalize: a must be [>= H, wa] and b [>= W, hb]")
+    selective = a[1] is not None
+    dev = a[0].device
+    new = lambda dt: torch.zeros(H, a[0].shape[1], dtype=dt, device=dev)  # noqa: E731
+    logit, mask, votes = new(torch.float32), new(torch.uint8), new(torch.uint8)
+    selection, sel_votes = (new(torch.float32), new(torch.uint8)) if selective else (None, None)
+    prob = new(torch.uint8) if prob8 else None
+    counts = torch.zeros(4, dtype=torch.int64, device=dev)  # uint64 bits
+    b = b or (None,) * 4
+    K.call("selunet_tta_finalize", *[K.ptr(t) for t in a], *[K.ptr(t) for t in b], members, H, W, a[0].shape[1],
+           0 if b[0] is None else b[0].shape[1], t_out, t_sel, K.ptr(logit), K.ptr(selection), K.ptr(mask),
+           K.ptr(prob), K.ptr(votes), K.ptr(sel_votes), K.ptr(counts), K.stream_ptr())
+    return (logit, selection, mask, prob, votes, sel_votes), counts
 
 
 @dataclass
 class Prediction:
     """`predict_image`'s result. logit, selection (None for a non-selective network), mask, prob8 (None when
     not asked for): device tensors [H,W], views of the canvases; counts: int64 numpy {background, tumor,
-    abstained, pixels} over the image; plan: the tiling used."""
+    abstained, pixels} over the image; plan: the tiling used. With test-time augmentation
+    logit and selection are the means over `members` orientations, and votes / sel_votes (uint8 [H,W]) count
+    the members with out >= t_out / sel >= t_sel; without it members is 1 and both are None (sel_votes also
+    for a non-selective network)."""
     logit: torch.Tensor
     selection: torch.Tensor | None
     mask: torch.Tensor
     prob8: torch.Tensor | None
     counts: np.ndarray
     plan: TilePlan
+    votes: torch.Tensor | None = None
+    sel_votes: torch.Tensor | None = None
+    members: int = 1
+
+    @property
+    def unanimous_fraction(self) -> float | None:
+        """The share of the image's pixels on which the members agree (votes 0 or all); None without votes."""
+        if self.votes is None:
+            return None
+        v = self.votes
+        return float(((v == 0) | (v == self.members)).sum().item()) / float(v.numel())
 
     @property
     def coverage(self) -> float:
@@ -173,9 +292,14 @@ class Prediction:
 
 def predict_image(net, image_u8, *, tile: int = 512, halo: int = HALO_MIN, batch_size: int = 16,
                   cut_off: float = 0.5, s_cut_off: float = 0.5, single_scale: str = "sigmoid",
-                  input_type: str = "RGB", prob8: bool = True, allow_small_halo: bool = False) -> Prediction:
+                  input_type: str = "RGB", prob8: bool = True, allow_small_halo: bool = False,
+                  tta: str = "none") -> Prediction:
     """Apply `net` (a UNet_B on a cuda device, in eval mode) to `image_u8`, a numpy or torch uint8 [H,W,3] RGB
-    image of any size: gather -> net -> stitch per batch of `batch_size` tiles, on the current stream."""
+    image of any size: gather -> net -> stitch per batch of `batch_size` tiles, on the current stream.
+    tta: "none", or "flips" / "d4": the mean over the 4 flips / the 8 flips and transposes of the image
+    (`TTA_MEMBERS`), with the votes of the members."""
+    if tta not in TTA_MEMBERS:
+        raise ValueError(f"predict_image: tta {tta!r}: one of {', '.join(map(repr, TTA_MEMBERS))}")
     if net.training:
         raise RuntimeError("predict_image needs the network in eval mode (net.eval()): tiling is exact only with "
                            "the running BatchNorm statistics")
@@ -192,6 +316,9 @@ def predict_image(net, image_u8, *, tile: int = 512, halo: int = HALO_MIN, batch
     t_out = MT.logit_threshold("eval", cut_off, single_scale)
     t_sel = MT.logit_threshold("eval", s_cut_off, single_scale)
     selective = bool(net.selective)
+    if tta != "none":
+        return _predict_tta(net, img, device, plan, TTA_MEMBERS[tta], batch_size, t_out, t_sel, input_type, prob8,
+                            allow_small_halo)
     with torch.cuda.device(device), torch.no_grad():
         img = img.to(device).contiguous()  # the one upload
         origins = torch.from_numpy(plan.origins).to(device)
@@ -212,6 +339,45 @@ def predict_image(net, image_u8, *, tile: int = 512, halo: int = HALO_MIN, batch
         host_counts = counts.cpu().numpy().astype(np.int64)  # the one read
     return Prediction(logit[:H, :W], None if selection is None else selection[:H, :W], mask[:H, :W],
                       None if prob is None else prob[:H, :W], host_counts, plan)
+
+
+def _predict_tta(net, img, device, plan, members, batch_size, t_out, t_sel, input_type, prob8, allow_small_halo):
+    """predict_image with test-time augmentation. Member k = 4 c + f is the prediction of the
+    image of orientation class c (0: the image; 1: its transpose, formed once on the device) flipped by f
+    (bit 1 rows, bit 0 columns), mapped back. Per class, members run one after another: flipped gather -> net
+    -> accumulate per batch of tiles into the class's fp32 sums and vote planes, whose rows are padded to a
+    multiple of 8 pixels (zeros, never written); one finalize forms the mean and everything derived from it."""
+    H, W, tile, halo = plan.H, plan.W, plan.tile, plan.halo
+    selective = bool(net.selective)
+    with torch.cuda.device(device), torch.no_grad():
+        img = img.to(device).contiguous()  # the one upload
+        x_buf = torch.empty(min(batch_size, plan.n), _CIN[input_type], tile, tile, dtype=torch.float32, device=device)
+        classes = []
+        for c in range(members // 4):
+            src = image_transpose(img) if c else img
+            h, w = int(src.shape[0]), int(src.shape[1])
+            p = TilePlan(h, w, tile, halo, allow_small_halo) if c else plan  # the member's own tiling
+            origins = torch.from_numpy(p.origins).to(device)
+            ws = -(-w // 8) * 8
+            sums = [torch.zeros(h, ws, dtype=torch.float32, device=device) if selective or i == 0 else None
+                    for i in range(2)]
+            vts = [torch.zeros(h, ws, dtype=torch.uint8, device=device) if selective or i == 0 else None
+                   for i in range(2)]
+            for f in range(4):
+                for a in range(0, p.n, batch_size):
+                    b = min(a + batch_size, p.n)
+                    x = tile_gather_flip(src, origins[a:b], tile, tile, input_type, f, out=x_buf[:b - a])
+                    res = net(x)
+                    out, sel = (res[0], res[1]) if selective else (res, None)
+                    tta_accumulate(out.contiguous(), None if sel is None else sel.contiguous(), p.origins[a:b],
+                                   origins[a:b], halo, f, f == 0, h, w, p.Hc, p.Wc, t_out, t_sel, sums[0], sums[1],
+                                   vts[0], vts[1])
+            classes.append((sums[0], sums[1], vts[0], vts[1]))
+        planes, counts = tta_finalize(classes[0], classes[1] if members == 8 else None, members, H, W, t_out, t_sel,
+                                      prob8)
+        host_counts = counts.cpu().numpy().astype(np.int64)  # the one read
+    logit, selection, mask, prob, votes, sel_votes = [None if t is None else t[:, :W] for t in planes]
+    return Prediction(logit, selection, mask, prob, host_counts, plan, votes, sel_votes, members)
 
 
 # ----------------------------------------------------------------------------- CLI
@@ -235,6 +401,8 @@ def parse_arguments(argv=None):
     # ---- tiling
     parser.add_argument('--tile', type=int, default=TILE_MAX, help='tile side, a multiple of 8, at most 512')
     parser.add_argument('--halo', type=int, default=HALO_MIN, help='halo, a multiple of 8, at least 56')
+    parser.add_argument('--tta', type=str, default='none', choices=list(TTA_MEMBERS),
+                        help='test-time augmentation: the mean over the 4 flips, or the 8 flips and transposes')
     args = parser.parse_args(argv)
     if args.fp32_path == 'split' and args.compute_dtype == 'bf16':
         parser.error('--fp32_path split is an fp32 path: not with --compute_dtype bf16')
@@ -279,7 +447,7 @@ def image_record(path, pred: Prediction) -> dict:
             "halo": pred.plan.halo, "grid": list(pred.plan.grid), "tiles": pred.plan.n,
             "counts": dict(zip(COUNT_NAMES, c)),
             "tumor_fraction_of_selected": c[1] / sel if sel else None,
-            "coverage": sel / c[3]}
+            "coverage": sel / c[3], "unanimous_fraction": pred.unanimous_fraction}
 
 
 def predict_files(args) -> dict:
@@ -301,18 +469,22 @@ def predict_files(args) -> dict:
     net = net.to(device).train(False)
     os.makedirs(args.save_dir, exist_ok=True)
     doc = {"checkpoint": ckpt, "selective": bool(args.selective), "input_type": args.input_type,
-           "cut_off": args.cut_off, "s_cut_off": args.s_cut_off, "single_scale": args.single_scale, "images": []}
+           "cut_off": args.cut_off, "s_cut_off": args.s_cut_off, "single_scale": args.single_scale, "tta": args.tta,
+           "images": []}
     for path in files:
         image = np.array(Image.open(path).convert("RGB"))
         pred = predict_image(net, image, tile=args.tile, halo=args.halo, batch_size=args.batch_size,
                              cut_off=args.cut_off, s_cut_off=args.s_cut_off, single_scale=args.single_scale,
-                             input_type=args.input_type)
+                             input_type=args.input_type, tta=args.tta)
         stem = os.path.join(args.save_dir, os.path.splitext(os.path.basename(path))[0])
         mask = pred.mask.cpu().numpy()
         Image.fromarray(mask).save(stem + "_mask.png")
         Image.fromarray(pred.prob8.cpu().numpy()).save(stem + "_prob.png")
         if args.selective:
             Image.fromarray(np.where(mask != 127, 255, 0).astype(np.uint8)).save(stem + "_select.png")
+        if pred.votes is not None:
+            votes = pred.votes.cpu().numpy().astype(np.int64)
+            Image.fromarray((votes * 255 // pred.members).astype(np.uint8)).save(stem + "_votes.png")
         rec = image_record(path, pred)
         doc["images"].append(rec)
         c = rec["counts"]

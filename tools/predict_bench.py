@@ -13,6 +13,13 @@ package had to do before `predict_image` existed — measurement tool.
     ceil(size / (tile - 112))^2 tiles), uploaded per batch, `data.prep_batch`, forward, both logit tensors
     copied back, eval.py's fp32 numpy sigmoid and `> cut_off` on the host. Host clock per stage, each stage
     ending in a synchronise.
+With `--tta` the tool times test-time augmentation instead (`... --tta > profiles/predict_tta.txt`,
+`... --tta --fp32_path split >> profiles/predict_tta.txt`): passes of `none` (pass (A) above), `flips` and `d4`
+(`predict_image`'s TTA loop restated around HIP events: transpose, flipped gather, forward, accumulate, finalize)
+alternate with (C), what a user does for `d4` without it: 8 plain `predict_image` calls on numpy-transformed
+copies, both planes to the host, un-flipped and averaged there, thresholds, `prob8` and counts in numpy (host
+clock per stage). Reported per mode: the pass, its ratio to K x the `none` pass of the same run, the summed time
+of the TTA-only kernels, their share of the pass and the bytes they move per second (bytes from the shapes).
 One warm-up pass, then `rounds` passes of (A) and (B) alternating; the median pass is reported with the
 min-max spread. Before timing, (A)'s mask is checked against the thresholds applied to its own planes, and
 (B)'s host mask against it away from the seams. Nothing here is a threshold: the tool records times.
@@ -121,6 +128,190 @@ def old_way(net, image, tile, batch, cut_off, dev):
     return ms, mask
 
 
+def tta_bytes(plan, members, selective=True):
+    """The bytes the TTA-only kernels of one pass move, from the shapes: {stage: bytes}."""
+    H, W, heads = plan.H, plan.W, 2 if selective else 1
+    tiles = 0
+    for c in range(members // 4):
+        p = plan if c == 0 else PR.TilePlan(W, H, plan.tile, plan.halo)
+        tiles += 4 * p.n
+    px = H * W
+    return {"transpose": 2 * 3 * px * (members // 8),
+            "gather": tiles * plan.tile * plan.tile * (3 + 3 * 4),
+            # per member and head: the core pixels inside the image read (4 B), the sum and the vote written
+            # (4 + 1 B) and, but for the class's first member, read before (4 + 1 B)
+            "accumulate": heads * px * (members * (4 + 5) + (members - members // 4) * 5),
+            # per class and head 4 + 1 B read; the two mean planes, mask, prob8 and the two vote planes written
+            "finalize": px * ((members // 4) * heads * 5 + heads * 5 + 2)}
+
+
+def tta_pass(net, image, plan, batch, t_out, t_sel, dev, members):
+    """One pass of predict_image(..., tta=) with an event after every stage: ({stage: ms}, planes, counts)."""
+    ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
+    marks, tr = [], []
+    H, W, tile, halo = plan.H, plan.W, plan.tile, plan.halo
+    with torch.no_grad():
+        t0 = ev()
+        t0.record()
+        img = torch.from_numpy(image).to(dev)
+        x_buf = torch.empty(min(batch, plan.n), 3, tile, tile, device=dev)
+        t1 = ev()
+        t1.record()
+        classes = []
+        for c in range(members // 4):
+            e = [ev(), ev()]
+            e[0].record()
+            src = PR.image_transpose(img) if c else img
+            e[1].record()
+            tr.append(e)
+            h, w = int(src.shape[0]), int(src.shape[1])
+            p = PR.TilePlan(h, w, tile, halo) if c else plan
+            origins = torch.from_numpy(p.origins).to(dev)
+            ws = -(-w // 8) * 8
+            sums = [torch.zeros(h, ws, device=dev) for _ in range(2)]
+            vts = [torch.zeros(h, ws, dtype=torch.uint8, device=dev) for _ in range(2)]
+            for f in range(4):
+                for a in range(0, p.n, batch):
+                    b = min(a + batch, p.n)
+                    e = [ev() for _ in range(4)]
+                    e[0].record()
+                    x = PR.tile_gather_flip(src, origins[a:b], tile, tile, "RGB", f, out=x_buf[:b - a])
+                    e[1].record()
+                    out, sel, _ = net(x)
+                    e[2].record()
+                    PR.tta_accumulate(out, sel, p.origins[a:b], origins[a:b], halo, f, f == 0, h, w, p.Hc, p.Wc, t_out,
+                                      t_sel, sums[0], sums[1], vts[0], vts[1])
+                    e[3].record()
+                    marks.append(e)
+            classes.append((sums[0], sums[1], vts[0], vts[1]))
+        t2 = ev()
+        t2.record()
+        planes, counts = PR.tta_finalize(classes[0], classes[1] if members == 8 else None, members, H, W, t_out, t_sel)
+        t3 = ev()
+        t3.record()
+        m, p8, v = planes[2][:, :W].cpu(), planes[3][:, :W].cpu(), planes[4][:, :W].cpu()
+        c = counts.cpu()
+        t4 = ev()
+        t4.record()
+        torch.cuda.synchronize()
+    ms = {"upload": t0.elapsed_time(t1), "transpose": sum(e[0].elapsed_time(e[1]) for e in tr[1:]),
+          "gather": sum(e[0].elapsed_time(e[1]) for e in marks), "forward": sum(e[1].elapsed_time(e[2]) for e in marks),
+          "accumulate": sum(e[2].elapsed_time(e[3]) for e in marks), "finalize": t2.elapsed_time(t3),
+          "final copy": t3.elapsed_time(t4), "whole pass": t0.elapsed_time(t4)}
+    return ms, [t[:, :W] for t in planes], c.numpy()
+
+
+def host_d4(net, image, tile, halo, batch, t_out, t_sel):
+    """(C): `d4` by hand around today's predict_image. ({stage: ms}, mean logit, mask)."""
+    ms = dict.fromkeys(("numpy transforms", "predict_image x 8", "planes to host", "un-flip + mean", "host thresholds"), 0.0)
+
+    def lap(name, t):
+        torch.cuda.synchronize()
+        now = time.perf_counter()
+        ms[name] += (now - t) * 1e3
+        return now
+
+    def turn(k, a):
+        a = a.swapaxes(0, 1) if k & 4 else a
+        a = a[::-1] if k & 2 else a
+        return a[:, ::-1] if k & 1 else a
+
+    def back(k, a):
+        a = a[:, ::-1] if k & 1 else a
+        a = a[::-1] if k & 2 else a
+        return a.T if k & 4 else a
+
+    t_all = t = time.perf_counter()
+    acc = [[None, None], [None, None]]  # [class][head], in the image's orientation
+    votes = 0
+    for k in range(8):
+        im = np.ascontiguousarray(turn(k, image))
+        t = lap("numpy transforms", t)
+        pred = PR.predict_image(net, im, tile=tile, halo=halo, batch_size=batch, prob8=False)
+        t = lap("predict_image x 8", t)
+        planes = [pred.logit.cpu().numpy(), pred.selection.cpu().numpy()]
+        t = lap("planes to host", t)
+        for i in range(2):
+            m = back(k, planes[i])
+            acc[k >> 2][i] = m.copy() if acc[k >> 2][i] is None else acc[k >> 2][i] + m
+        votes = votes + (back(k, planes[0]) >= np.float32(t_out)).astype(np.uint8)
+        t = lap("un-flip + mean", t)
+    mean = [(acc[0][i] + acc[1][i]) * np.float32(0.125) for i in range(2)]
+    t = lap("un-flip + mean", t)
+    with np.errstate(over="ignore"):
+        mask = np.where(~(mean[1] >= np.float32(t_sel)), 127, np.where(mean[0] >= np.float32(t_out), 255, 0)).astype(np.uint8)
+        prob8 = np.floor(255.0 / (1.0 + np.exp(-mean[0])) + 0.5).astype(np.uint8)
+        counts = [int((mask == 0).sum()), int((mask == 255).sum()), int((mask == 127).sum()), mask.size]
+    t = lap("host thresholds", t)
+    ms["whole pass"] = (time.perf_counter() - t_all) * 1e3
+    return ms, mean[0], mask, votes, counts, prob8
+
+
+def tta_report(a, net, image, plan, t_out, t_sel, dev, mpix):
+    """--tta: passes of none, flips, d4 and the host-side d4 alternating; the report of the module docstring."""
+    modes = {"none": 1, "flips": 4, "d4": 8}
+    run = {"none": lambda: staged_pass(net, image, plan, a.batch, t_out, t_sel, dev)[0],
+           "flips": lambda: tta_pass(net, image, plan, a.batch, t_out, t_sel, dev, 4)[0],
+           "d4": lambda: tta_pass(net, image, plan, a.batch, t_out, t_sel, dev, 8)[0]}
+    # ---- warm-up and checks: the restated loop against predict_image, and against the host-side mean
+    ok = True
+    for mode in ("flips", "d4"):
+        _, planes, counts = tta_pass(net, image, plan, a.batch, t_out, t_sel, dev, modes[mode])
+        pred = PR.predict_image(net, image, tile=a.tile, halo=a.halo, batch_size=a.batch, tta=mode)
+        same = bool(torch.equal(planes[0], pred.logit)) and bool(torch.equal(planes[2], pred.mask)) and \
+            bool(torch.equal(planes[4], pred.votes)) and counts.tolist() == pred.counts.tolist()
+        print(f"({mode}) restated loop == predict_image(tta={mode!r}): {same}; counts "
+              f"{dict(zip(PR.COUNT_NAMES, counts.tolist()))}, unanimous fraction {pred.unanimous_fraction:.4f}")
+        ok = ok and same
+    _, mean, mask, votes, hcounts, _ = host_d4(net, image, a.tile, a.halo, a.batch, t_out, t_sel)
+    d = float(np.abs(mean - planes[0].cpu().numpy()).max())
+    same = d == 0.0 and bool(np.array_equal(mask, planes[2].cpu().numpy())) and \
+        bool(np.array_equal(votes, planes[4].cpu().numpy())) and hcounts == counts.tolist()
+    print(f"(C) host-side d4 mean vs the device's: max |difference| {d}; mask, votes and counts equal: {same}")
+    ok = ok and same
+    run["none"]()
+    # ---- timing
+    ts = {m: [] for m in modes}
+    tc = []
+    for _ in range(a.rounds):
+        for m in modes:
+            ts[m].append(run[m]())
+        tc.append(host_d4(net, image, a.tile, a.halo, a.batch, t_out, t_sel)[0])
+
+    def row(rows, k):
+        v = [t[k] for t in rows]
+        return statistics.median(v), f"{statistics.median(v):10.2f} [{min(v):.2f} .. {max(v):.2f}]"
+
+    none, s = row(ts["none"], "whole pass")
+    v = [t["whole pass"] for t in ts["none"]]
+    spread = (max(v) - min(v)) / none
+    print("(none) pass (A): gather, forward, stitch (HIP events, summed over the batches of a pass)")
+    for k in ("upload", "gather", "forward", "stitch", "final copy", "whole pass"):
+        print(f"    {k:<22}{row(ts['none'], k)[1]}")
+    print(f"    spread of the passes (max - min) / median: {spread:.4f}")
+    for mode in ("flips", "d4"):
+        K = modes[mode]
+        by = tta_bytes(plan, K)
+        print(f"({mode}) {K} members: transpose, flipped gather, forward, accumulate, finalize")
+        med = {}
+        for k in ("upload", "transpose", "gather", "forward", "accumulate", "finalize", "final copy", "whole pass"):
+            med[k], s = row(ts[mode], k)
+            gbs = f"  {by[k] / 1e6:9.1f} MB, {by[k] / med[k] / 1e6:7.1f} GB/s" if k in by and med[k] > 0 else ""
+            print(f"    {k:<22}{s}{gbs}")
+        only = sum(med[k] for k in by)
+        print(f"    TTA-only kernels (transpose + gather + accumulate + finalize): {only:.2f} ms = {only / med['whole pass']:.4f} "
+              f"of the pass, {sum(by.values()) / only / 1e6:.1f} GB/s over them")
+        print(f"    whole pass / ({K} x the none pass): {med['whole pass'] / (K * none):.4f}; "
+              f"{mpix / med['whole pass'] * 1e3:.1f} Mpixel/s")
+    print("(C) d4 on the host: 8 x predict_image, planes to the host, numpy un-flip, mean, thresholds (host clock per stage)")
+    for k in ("numpy transforms", "predict_image x 8", "planes to host", "un-flip + mean", "host thresholds", "whole pass"):
+        m, s = row(tc, k)
+        print(f"    {k:<22}{s}")
+    print(f"    (C) / (d4) whole pass = {row(tc, 'whole pass')[0] / row(ts['d4'], 'whole pass')[0]:.2f}")
+    print("checks passed:", ok)
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=4096)
@@ -130,6 +321,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--compute_dtype", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--fp32_path", default="exact", choices=["exact", "split"])
+    ap.add_argument("--tta", action="store_true", help="time test-time augmentation: none, flips, d4 and d4 on the host")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("predict_bench: no GPU visible (timings are taken on the device only)")
@@ -154,6 +346,8 @@ def main():
     print(f"{torch.cuda.get_device_name(0)}; {a.size} x {a.size} image ({mpix:.1f} Mpixel), selective UNet_B "
           f"{a.compute_dtype} ({a.fp32_path}), batch {a.batch}; median of {a.rounds} passes [min .. max], ms")
     print(f"(A) {plan!r}: {plan.n} tiles in {-(-plan.n // a.batch)} batches")
+    if a.tta:
+        return tta_report(a, net, image, plan, t_out, t_sel, dev, mpix)
     n_old = (a.size // a.tile) ** 2
     print(f"(B) {n_old} patches of {a.tile} x {a.tile} without halo in {-(-n_old // a.batch)} batches")
 
