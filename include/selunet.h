@@ -808,6 +808,49 @@ int selunet_tta_finalize(const float* a_out, const float* a_sel, const uint8_t* 
                          float* sel_plane, uint8_t* mask, uint8_t* prob8, uint8_t* votes, uint8_t* sel_votes,
                          unsigned long long* counts, void* stream);
 
+/* ---- connected regions of a prediction mask ----------------------------------
+ * A region of value v of a uint8 mask [H][W] is a maximal set of pixels equal to v connected under
+ * connectivity 4 or 8; its label is 1 + y W + x of its first pixel in raster order. mask is a view: row y
+ * starts mask_pitch bytes after row y - 1, at any alignment. All three calls: EINVAL for H or W < 1,
+ * H * W >= 2^31 - 1, a pitch below W. Integer arithmetic and integer atomics only: every result is the
+ * same bit for bit on every run. */
+/* Labels the regions of `value`: local union-find per 64 x 64 tile, unions across the tile borders by
+ * agent-scope atomic minima, then every pixel replaced by its root (three launches on `stream`).
+ *   parent: uint32 [H][lp] scratch, lp = W rounded up to a multiple of 4; holds no result afterwards;
+ *   labels: int32 [H][lp] = the label of the pixel's region, 0 where the pixel is not `value` and in the
+ *     padding columns x >= W;
+ *   roots: uint8 [H][lp] = 1 where the pixel is the first of its region, else 0;
+ *   err: uint32 [1], caller-zeroed, |= 1 / 2 / 4 if a loop of the local / seam / flatten pass reached its
+ *     iteration cap (never on an intact plane: the words of a chain strictly decrease);
+ *   passes: 7 for a labelling; a subset of 1 local, 2 seam, 4 flatten launches only those (to time a pass:
+ *     the passes of one labelling must then be issued in that order on one stream, with the same arguments).
+ * Also EINVAL: passes outside [1, 7]; a null pointer; value outside [0, 255]; connectivity not 4 or 8; lp not W rounded up to 4;
+ * H * lp >= 2^32 - 1; parent or labels not 16-B aligned, roots or err not 4-B aligned. */
+int selunet_regions_label(const uint8_t* mask, int64_t mask_pitch, int32_t H, int32_t W, int32_t value,
+                          int32_t connectivity, uint32_t* parent, int32_t* labels, uint8_t* roots,
+                          int32_t lp, uint32_t* err, int32_t passes, void* stream);
+/* The region table. labels: int32 rows of lp words as selunet_regions_label's; rowidx: int32 rows of rp
+ * words holding, at the position (y, x) of every region's first pixel, the region's row in [0, n_rows).
+ * table: uint64 [9][n_rows], columns {area, y_min, x_min, y_max, x_max, sum_y, sum_x, prob_sum,
+ * abstain_contacts}; the caller sets the minima to a value >= H, W and the rest to 0. prob_sum sums prob8
+ * (uint8 rows of prob_pitch bytes, nullable: the column is then left alone); abstain_contacts counts the
+ * ordered pairs (pixel of the region, 4-neighbour inside the image) whose neighbour is 127 in `mask`.
+ * A label outside [1, H W] or a row outside [0, n_rows) is skipped. Also EINVAL: null labels, mask, rowidx
+ * or table; n_rows outside [1, H W]; labels or rowidx not 4-B aligned, table not 8-B aligned. */
+int selunet_regions_stats(const int32_t* labels, int32_t lp, const uint8_t* mask, int64_t mask_pitch,
+                          const uint8_t* prob8, int64_t prob_pitch, int32_t H, int32_t W,
+                          const int32_t* rowidx, int32_t rp, int64_t n_rows, unsigned long long* table,
+                          void* stream);
+/* Rewrites the mask in place: a pixel of a region whose action[row] (uint8 [n_rows]) is 1 becomes 0, 2
+ * becomes 255, 0 stays; pixels without a label stay. counts: uint64 [4], caller-zeroed, += {pixels equal
+ * to 0, to 255, to 127, their sum} of the resulting mask. labels, rowidx and action all null: the mask is
+ * only counted. Bytes outside the [H][W] view are neither read nor written. Also EINVAL: null mask or
+ * counts; only some of labels, rowidx, action given; n_rows outside [1, H W]; labels or rowidx not 4-B
+ * aligned; counts not 8-B aligned. */
+int selunet_regions_apply(uint8_t* mask, int64_t mask_pitch, int32_t H, int32_t W, const int32_t* labels,
+                          int32_t lp, const int32_t* rowidx, int32_t rp, const uint8_t* action,
+                          int64_t n_rows, unsigned long long* counts, void* stream);
+
 /* ---- multi-GPU overlap probe (bench/tools only, not on the training path) ------
  * Stand-in for one bucketed RCCL all-reduce kernel on a single GPU: n_wg workgroups of 256 threads
  * reduce-copy dst[i] += src[i] over their slices of [0, n) (n % 4 == 0, 16-B aligned), repeatedly,

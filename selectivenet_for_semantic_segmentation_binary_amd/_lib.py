@@ -206,6 +206,11 @@ SIGNATURES = {
     "selunet_image_transpose": (c_int32, [P, c_int32, c_int32, P, P]),
     "selunet_tta_accumulate": (c_int32, [P, P, P] + [c_int32] * 9 + [c_float, c_float, P, P, P, P, P]),
     "selunet_tta_finalize": (c_int32, [P] * 8 + [c_int32] * 5 + [c_float, c_float] + [P] * 8),
+    "selunet_regions_label": (c_int32, [P, c_int64, c_int32, c_int32, c_int32, c_int32, P, P, P, c_int32, P, c_int32,
+                                        P]),
+    "selunet_regions_stats": (c_int32, [P, c_int32, P, c_int64, P, c_int64, c_int32, c_int32, P, c_int32, c_int64, P,
+                                        P]),
+    "selunet_regions_apply": (c_int32, [P, c_int64, c_int32, c_int32, P, c_int32, P, c_int32, P, c_int64, P, P]),
     "selunet_set_option": (c_int64, [c_int32, c_int64]),
     "selunet_cu_hold": (c_int32, [P, P, c_int64, c_int32, c_float, P]),
 }

@@ -23,6 +23,13 @@ the selected pixels and the coverage. Thresholds are `metrics.logit_threshold(ru
 transposes of the image on the device; the mask, the probability map and the counts then come from
 the means, `<stem>_votes.png` (L: votes * 255 // members) shows how many orientations say tumor, and predict.json
 carries "tta" and per image "unanimous_fraction", the share of pixels on which all orientations agree.
+
+`--regions 1`, `--min_region N`, `--fill_holes M`, `--connectivity {4,8}` (`predict_image(..., regions=, min_region=,
+fill_holes=, connectivity=)`) label the tumor regions of the mask on the device, remove regions of fewer
+than N pixels, fill enclosed background holes of at most M pixels that touch no abstained pixel, and report the
+regions of the cleaned mask: `<stem>_mask.png` is then the cleaned mask, `<stem>_regions.csv` holds one row per region
+(exact integer columns plus centroid and mean probability), and the image's predict.json entry gains "regions",
+"largest_region_area" and "cleanup". Without these flags nothing of that runs and every file is as before.
 """
 from __future__ import annotations
 
@@ -252,6 +259,225 @@ def tta_finalize(a, b, members: int, H: int, W: int, t_out: float, t_sel: float,
     return (logit, selection, mask, prob, votes, sel_votes), counts
 
 
+# ----------------------------------------------------------------------------- regions
+REGION_COLUMNS = ("label", "area", "y_min", "x_min", "y_max", "x_max", "sum_y", "sum_x", "prob_sum",
+                  "abstain_contacts")
+REGION_PIXELS_MAX = 2 ** 31 - 1  # labels are int32: 1 + y W + x
+CLEANUP_NAMES = ("removed_regions", "removed_pixels", "filled_holes", "filled_pixels")
+_REGION_PASSES = ((1, "local"), (2, "seam"), (4, "flatten"))
+_TABLE_MIN_INIT = 2 ** 62
+
+
+@dataclass
+class Regions:
+    """The region table: one int64 tensor [n] per column of REGION_COLUMNS, rows ascending by label. prob_sum
+    is None when no prob8 plane was given. Every value is an exact integer; the centroid is
+    (sum_y / area, sum_x / area) and the mean probability prob_sum / (255 area), formed on the host."""
+    label: torch.Tensor
+    area: torch.Tensor
+    y_min: torch.Tensor
+    x_min: torch.Tensor
+    y_max: torch.Tensor
+    x_max: torch.Tensor
+    sum_y: torch.Tensor
+    sum_x: torch.Tensor
+    prob_sum: torch.Tensor | None
+    abstain_contacts: torch.Tensor
+
+    def __len__(self) -> int:
+        return int(self.label.numel())
+
+    def columns(self) -> tuple:
+        return tuple(c for c in REGION_COLUMNS if getattr(self, c) is not None)
+
+    def numpy(self) -> dict:
+        """{column: int64 numpy [n]} in one transfer."""
+        cols = self.columns()
+        host = torch.stack([getattr(self, c) for c in cols]).cpu().numpy().astype(np.int64)
+        return {c: host[i] for i, c in enumerate(cols)}
+
+    def rows(self) -> list:
+        """One dict of Python ints per region."""
+        host = self.numpy()
+        return [{c: int(v[i]) for c, v in host.items()} for i in range(len(self))]
+
+
+def _region_args(fn, min_region, fill_holes, connectivity):
+    if connectivity not in (4, 8):
+        raise ValueError(f"{fn}: connectivity {connectivity!r}: 4 or 8")
+    for name, v in (("min_region", min_region), ("fill_holes", fill_holes)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0:
+            raise ValueError(f"{fn}: {name} must be an integer >= 0 (got {v!r})")
+
+
+def _region_size(fn, H, W):
+    if H < 1 or W < 1 or H * W >= REGION_PIXELS_MAX:
+        raise ValueError(f"{fn}: region labels need 1 <= H * W < 2^31 - 1 (got {H} x {W})")
+
+
+def _plane(fn, name, t, dtype, H=None, W=None):
+    """A 2-d cuda view whose rows are contiguous; returns its row pitch in elements."""
+    if (not torch.is_tensor(t) or t.device.type != "cuda" or t.dtype != dtype or t.dim() != 2
+            or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1])):
+        raise ValueError(f"{fn}: {name} must be a cuda {dtype} [H,W] tensor or a view of one with contiguous rows")
+    if H is not None and tuple(t.shape) != (H, W):
+        raise ValueError(f"{fn}: {name} must be [{H},{W}] like the mask (got {tuple(t.shape)})")
+    return max(int(t.stride(0)), int(t.shape[1])) if t.shape[0] > 1 else int(t.shape[1])
+
+
+class _Labelling:
+    """One labelling: labels int32 [H,lp] (lp = W rounded up to 4), the positions and labels of the roots in
+    ascending order, the plane holding each root's row at the root's position, and the device error word."""
+
+    def __init__(self, H, W, lp, labels, rowidx, rp, label_col, err):
+        self.H, self.W, self.lp, self.labels, self.rowidx, self.rp = H, W, lp, labels, rowidx, rp
+        self.label_col, self.err = label_col, err
+
+    @property
+    def n(self) -> int:
+        return int(self.label_col.numel())
+
+
+def _raise_region_error(word: int):
+    if word:
+        names = ", ".join(n for b, n in _REGION_PASSES if word & b)
+        raise K.SelunetError(f"selunet_regions_label: the {names} pass reached its iteration cap (error word {word}): "
+                             "the label plane was corrupted while it ran")
+
+
+def _label(fn, mask, value, connectivity) -> _Labelling:
+    pitch = _plane(fn, "mask", mask, torch.uint8)
+    H, W = int(mask.shape[0]), int(mask.shape[1])
+    _region_size(fn, H, W)
+    if not 0 <= int(value) <= 255:
+        raise ValueError(f"{fn}: value must be in [0, 255] (got {value!r})")
+    lp = -(-W // 4) * 4
+    dev = mask.device
+    with torch.cuda.device(dev):
+        parent = torch.empty(H, lp, dtype=torch.int32, device=dev)  # uint32 bits
+        labels = torch.empty(H, lp, dtype=torch.int32, device=dev)
+        roots = torch.empty(H, lp, dtype=torch.uint8, device=dev)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        K.call("selunet_regions_label", K.ptr(mask), pitch, H, W, int(value), int(connectivity), K.ptr(parent),
+               K.ptr(labels), K.ptr(roots), lp, K.ptr(err), 7, K.stream_ptr())
+        # the roots into ascending rows, once per labelling: raster order is label order. The parent plane
+        # is done with; it becomes the root-indexed plane of row numbers.
+        pos = torch.nonzero(roots.view(-1)).view(-1)
+        parent.view(-1)[pos] = torch.arange(pos.numel(), dtype=torch.int32, device=dev)
+        label_col = 1 + torch.div(pos, lp, rounding_mode="floor") * W + pos % lp
+    return _Labelling(H, W, lp, labels, parent, lp, label_col, err)
+
+
+def label_regions(mask: torch.Tensor, value: int = 255, connectivity: int = 8):
+    """`selunet_regions_label`: the regions of `value` of a cuda uint8 [H,W] mask (possibly a view of a canvas)
+    under connectivity 4 or 8. Returns (labels, n_regions): int32 [H,W], a view of a plane with padded rows,
+    holding 1 + y W + x of the first pixel of each pixel's region (0 where the mask is not `value`)."""
+    _region_args("label_regions", 0, 0, connectivity)
+    lab = _label("label_regions", mask, value, connectivity)
+    _raise_region_error(int(lab.err.item()))
+    labels = lab.labels[:, :lab.W]
+    labels._selunet_labelling = lab  # region_table finds the roots here instead of searching the plane again
+    return labels, lab.n
+
+
+def _labelling_of(fn, labels, H, W) -> _Labelling:
+    lab = getattr(labels, "_selunet_labelling", None)
+    if lab is not None and (lab.H, lab.W) == (H, W) and labels.data_ptr() == lab.labels.data_ptr():
+        return lab
+    # any int32 label plane in canonical form: its roots are the pixels that hold their own index
+    lp = _plane(fn, "labels", labels, torch.int32, H, W)
+    dev = labels.device
+    own = (1 + torch.arange(H, dtype=torch.int32, device=dev)[:, None] * W
+           + torch.arange(W, dtype=torch.int32, device=dev)[None, :])
+    pos = torch.nonzero((labels == own).reshape(-1)).view(-1)
+    rowidx = torch.empty(H, W, dtype=torch.int32, device=dev)
+    rowidx.view(-1)[pos] = torch.arange(pos.numel(), dtype=torch.int32, device=dev)
+    return _Labelling(H, W, lp, labels, rowidx, W, pos + 1, None)
+
+
+def _table(fn, mask, lab: _Labelling, prob8) -> Regions:
+    pitch = _plane(fn, "mask", mask, torch.uint8, lab.H, lab.W)
+    ppitch = 0 if prob8 is None else _plane(fn, "prob8", prob8, torch.uint8, lab.H, lab.W)
+    n, dev = lab.n, mask.device
+    with torch.cuda.device(dev):
+        table = torch.zeros(9, n, dtype=torch.int64, device=dev)  # uint64 bits
+        table[1:3] = _TABLE_MIN_INIT
+        if n:
+            K.call("selunet_regions_stats", K.ptr(lab.labels), lab.lp, K.ptr(mask), pitch, K.ptr(prob8), ppitch, lab.H,
+                   lab.W, K.ptr(lab.rowidx), lab.rp, n, K.ptr(table), K.stream_ptr())
+    return Regions(lab.label_col, table[0], table[1], table[2], table[3], table[4], table[5], table[6],
+                   None if prob8 is None else table[7], table[8])
+
+
+def region_table(mask: torch.Tensor, labels: torch.Tensor, prob8: torch.Tensor | None = None) -> Regions:
+    """`selunet_regions_stats`: the table of the regions that `labels` (label_regions' result, or any int32
+    [H,W] plane in its form) marks in `mask`; prob8 (uint8 [H,W]) adds the column prob_sum."""
+    _plane("region_table", "mask", mask, torch.uint8)
+    H, W = int(mask.shape[0]), int(mask.shape[1])
+    _region_size("region_table", H, W)
+    if not torch.is_tensor(labels) or tuple(labels.shape) != (H, W):
+        raise ValueError(f"region_table: labels must be [{H},{W}] like the mask")
+    return _table("region_table", mask, _labelling_of("region_table", labels, H, W), prob8)
+
+
+def _apply(fn, mask, lab, action, counts):
+    pitch = _plane(fn, "mask", mask, torch.uint8)
+    H, W = int(mask.shape[0]), int(mask.shape[1])
+    with torch.cuda.device(mask.device):
+        if lab is None:
+            K.call("selunet_regions_apply", K.ptr(mask), pitch, H, W, None, 0, None, 0, None, 0, K.ptr(counts),
+                   K.stream_ptr())
+        else:
+            _check(f"{fn}: action", action, torch.uint8)
+            K.call("selunet_regions_apply", K.ptr(mask), pitch, H, W, K.ptr(lab.labels), lab.lp, K.ptr(lab.rowidx),
+                   lab.rp, K.ptr(action), lab.n, K.ptr(counts), K.stream_ptr())
+
+
+def clean_mask(mask: torch.Tensor, prob8: torch.Tensor | None = None, min_region: int = 0, fill_holes: int = 0,
+               connectivity: int = 8):
+    """The clean-up of DESIGN.md §7h on a 0 / 127 / 255 mask, in place: (1) min_region = N > 0: every region of
+    255 under `connectivity` with area < N becomes 0; (2) fill_holes = M > 0: every region of 0 under the
+    complementary connectivity whose bounding box touches no image border, that has no abstained 4-neighbour
+    and whose area is <= M becomes 255. Returns (Regions of the 255-regions of the final mask, counts int64 [4]
+    {background, tumor, abstained, pixels} of it, removed_regions, removed_pixels, filled_holes, filled_pixels);
+    the scalars, the counts and the kernels' error word arrive in one read."""
+    fn = "clean_mask"
+    _region_args(fn, min_region, fill_holes, connectivity)
+    _plane(fn, "mask", mask, torch.uint8)
+    H, W = int(mask.shape[0]), int(mask.shape[1])
+    _region_size(fn, H, W)
+    if prob8 is not None:
+        _plane(fn, "prob8", prob8, torch.uint8, H, W)
+    dev = mask.device
+    with torch.cuda.device(dev):
+        scal = torch.zeros(9, dtype=torch.int64, device=dev)  # counts[4], CLEANUP_NAMES[4], error word
+        spare = torch.zeros(4, dtype=torch.int64, device=dev)
+        if min_region > 0:
+            lab = _label(fn, mask, 255, connectivity)
+            scal[8:9] |= lab.err
+            if lab.n:
+                reg = _table(fn, mask, lab, None)
+                drop = reg.area < int(min_region)
+                _apply(fn, mask, lab, drop.to(torch.uint8), spare)
+                scal[4], scal[5] = drop.sum(), (reg.area * drop).sum()
+        if fill_holes > 0:
+            lab = _label(fn, mask, 0, 12 - connectivity)
+            scal[8:9] |= lab.err
+            if lab.n:
+                reg = _table(fn, mask, lab, None)
+                fill = ((reg.y_min > 0) & (reg.x_min > 0) & (reg.y_max < H - 1) & (reg.x_max < W - 1)
+                        & (reg.abstain_contacts == 0) & (reg.area <= int(fill_holes)))
+                _apply(fn, mask, lab, fill.to(torch.uint8) * 2, spare)
+                scal[6], scal[7] = fill.sum(), (reg.area * fill).sum()
+        lab = _label(fn, mask, 255, connectivity)
+        scal[8:9] |= lab.err
+        regions = _table(fn, mask, lab, prob8)
+        _apply(fn, mask, None, None, scal)  # counts into scal[0:4]
+        host = scal.cpu().numpy().astype(np.int64)  # the one read
+    _raise_region_error(int(host[8]))
+    return (regions, host[:4].copy()) + tuple(int(v) for v in host[4:8])
+
+
 @dataclass
 class Prediction:
     """`predict_image`'s result. logit, selection (None for a non-selective network), mask, prob8 (None when
@@ -269,6 +495,8 @@ class Prediction:
     votes: torch.Tensor | None = None
     sel_votes: torch.Tensor | None = None
     members: int = 1
+    regions: Regions | None = None  # with region analysis: the tumor regions of the final mask
+    cleanup: dict | None = None     # and {removed_regions, removed_pixels, filled_holes, filled_pixels}
 
     @property
     def unanimous_fraction(self) -> float | None:
@@ -293,11 +521,15 @@ class Prediction:
 def predict_image(net, image_u8, *, tile: int = 512, halo: int = HALO_MIN, batch_size: int = 16,
                   cut_off: float = 0.5, s_cut_off: float = 0.5, single_scale: str = "sigmoid",
                   input_type: str = "RGB", prob8: bool = True, allow_small_halo: bool = False,
-                  tta: str = "none") -> Prediction:
+                  tta: str = "none", regions: bool = False, min_region: int = 0, fill_holes: int = 0,
+                  connectivity: int = 8) -> Prediction:
     """Apply `net` (a UNet_B on a cuda device, in eval mode) to `image_u8`, a numpy or torch uint8 [H,W,3] RGB
     image of any size: gather -> net -> stitch per batch of `batch_size` tiles, on the current stream.
     tta: "none", or "flips" / "d4": the mean over the 4 flips / the 8 flips and transposes of the image
-    (`TTA_MEMBERS`), with the votes of the members."""
+    (`TTA_MEMBERS`), with the votes of the members.
+    regions / min_region / fill_holes / connectivity: with `regions` or a clean-up size > 0 the
+    mask is cleaned in place (`clean_mask`), counts are those of the cleaned mask, and `regions` / `cleanup`
+    hold the table of its tumor regions and what the clean-up did; with the defaults nothing of that runs."""
     if tta not in TTA_MEMBERS:
         raise ValueError(f"predict_image: tta {tta!r}: one of {', '.join(map(repr, TTA_MEMBERS))}")
     if net.training:
@@ -313,9 +545,24 @@ def predict_image(net, image_u8, *, tile: int = 512, halo: int = HALO_MIN, batch
         raise ValueError(f"predict_image: the image must be uint8 [H,W,3] RGB (got {img.dtype} {tuple(img.shape)})")
     H, W = int(img.shape[0]), int(img.shape[1])
     plan = TilePlan(H, W, tile, halo, allow_small_halo)
+    _region_args("predict_image", min_region, fill_holes, connectivity)
+    analyse = bool(regions) or min_region > 0 or fill_holes > 0
+    if analyse:
+        _region_size("predict_image", H, W)
+        if regions and not prob8:
+            raise ValueError("predict_image: regions=True reports prob_sum, which needs prob8=True")
     t_out = MT.logit_threshold("eval", cut_off, single_scale)
     t_sel = MT.logit_threshold("eval", s_cut_off, single_scale)
     selective = bool(net.selective)
+    if analyse:
+        pred = predict_image(net, img, tile=tile, halo=halo, batch_size=batch_size, cut_off=cut_off,
+                             s_cut_off=s_cut_off, single_scale=single_scale, input_type=input_type, prob8=prob8,
+                             allow_small_halo=allow_small_halo, tta=tta)
+        with torch.cuda.device(device):  # the stages read the mask and prob8 only: any forward path, any tta
+            pred.regions, pred.counts, *done = clean_mask(pred.mask, pred.prob8, int(min_region), int(fill_holes),
+                                                          connectivity)
+        pred.cleanup = dict(zip(CLEANUP_NAMES, done))
+        return pred
     if tta != "none":
         return _predict_tta(net, img, device, plan, TTA_MEMBERS[tta], batch_size, t_out, t_sel, input_type, prob8,
                             allow_small_halo)
@@ -403,9 +650,19 @@ def parse_arguments(argv=None):
     parser.add_argument('--halo', type=int, default=HALO_MIN, help='halo, a multiple of 8, at least 56')
     parser.add_argument('--tta', type=str, default='none', choices=list(TTA_MEMBERS),
                         help='test-time augmentation: the mean over the 4 flips, or the 8 flips and transposes')
+    # ---- region analysis and clean-up of the mask
+    parser.add_argument('--regions', type=int, default=0, choices=[0, 1],
+                        help='1: write <stem>_regions.csv, the table of the tumor regions')
+    parser.add_argument('--min_region', type=int, default=0, help='remove tumor regions of fewer pixels (0: off)')
+    parser.add_argument('--fill_holes', type=int, default=0,
+                        help='fill background holes of at most this many pixels inside tumor (0: off)')
+    parser.add_argument('--connectivity', type=int, default=8, choices=[4, 8],
+                        help='connectivity of tumor regions; holes use the complementary one')
     args = parser.parse_args(argv)
     if args.fp32_path == 'split' and args.compute_dtype == 'bf16':
         parser.error('--fp32_path split is an fp32 path: not with --compute_dtype bf16')
+    if args.min_region < 0 or args.fill_holes < 0:
+        parser.error('--min_region and --fill_holes must be >= 0')
     return args
 
 
@@ -443,11 +700,36 @@ def image_record(path, pred: Prediction) -> dict:
     """One image's entry of predict.json."""
     c = [int(v) for v in pred.counts]
     sel = c[0] + c[1]
-    return {"input": path, "height": pred.plan.H, "width": pred.plan.W, "tile": pred.plan.tile,
-            "halo": pred.plan.halo, "grid": list(pred.plan.grid), "tiles": pred.plan.n,
-            "counts": dict(zip(COUNT_NAMES, c)),
-            "tumor_fraction_of_selected": c[1] / sel if sel else None,
-            "coverage": sel / c[3], "unanimous_fraction": pred.unanimous_fraction}
+    rec = {"input": path, "height": pred.plan.H, "width": pred.plan.W, "tile": pred.plan.tile,
+           "halo": pred.plan.halo, "grid": list(pred.plan.grid), "tiles": pred.plan.n,
+           "counts": dict(zip(COUNT_NAMES, c)),
+           "tumor_fraction_of_selected": c[1] / sel if sel else None,
+           "coverage": sel / c[3], "unanimous_fraction": pred.unanimous_fraction}
+    if pred.regions is not None:  # only with region analysis: a plain run's file is what it was
+        rec["regions"] = len(pred.regions)
+        rec["largest_region_area"] = int(pred.regions.area.max().item()) if len(pred.regions) else 0
+        rec["cleanup"] = {k: int(v) for k, v in pred.cleanup.items()}
+    return rec
+
+
+def region_csv_rows(regions: Regions) -> list:
+    """The lines of <stem>_regions.csv: a header, then per region the table's columns and centroid_y = sum_y / area,
+    centroid_x = sum_x / area, mean_prob = prob_sum / (255 area) (when prob_sum is there), each the correctly
+    rounded quotient of the two integers, written by repr."""
+    cols = regions.columns()
+    derived = ("centroid_y", "centroid_x") + (("mean_prob",) if "prob_sum" in cols else ())
+    lines = [",".join(cols + derived)]
+    for r in regions.rows():
+        vals = [str(r[c]) for c in cols] + [repr(r["sum_y"] / r["area"]), repr(r["sum_x"] / r["area"])]
+        if "prob_sum" in cols:
+            vals.append(repr(r["prob_sum"] / (255 * r["area"])))
+        lines.append(",".join(vals))
+    return lines
+
+
+def write_regions_csv(path, regions: Regions):
+    with open(path, "w") as fh:
+        fh.write("\n".join(region_csv_rows(regions)) + "\n")
 
 
 def predict_files(args) -> dict:
@@ -475,7 +757,8 @@ def predict_files(args) -> dict:
         image = np.array(Image.open(path).convert("RGB"))
         pred = predict_image(net, image, tile=args.tile, halo=args.halo, batch_size=args.batch_size,
                              cut_off=args.cut_off, s_cut_off=args.s_cut_off, single_scale=args.single_scale,
-                             input_type=args.input_type, tta=args.tta)
+                             input_type=args.input_type, tta=args.tta, regions=bool(args.regions),
+                             min_region=args.min_region, fill_holes=args.fill_holes, connectivity=args.connectivity)
         stem = os.path.join(args.save_dir, os.path.splitext(os.path.basename(path))[0])
         mask = pred.mask.cpu().numpy()
         Image.fromarray(mask).save(stem + "_mask.png")
@@ -485,6 +768,8 @@ def predict_files(args) -> dict:
         if pred.votes is not None:
             votes = pred.votes.cpu().numpy().astype(np.int64)
             Image.fromarray((votes * 255 // pred.members).astype(np.uint8)).save(stem + "_votes.png")
+        if pred.regions is not None:
+            write_regions_csv(stem + "_regions.csv", pred.regions)
         rec = image_record(path, pred)
         doc["images"].append(rec)
         c = rec["counts"]

@@ -20,6 +20,13 @@ alternate with (C), what a user does for `d4` without it: 8 plain `predict_image
 copies, both planes to the host, un-flipped and averaged there, thresholds, `prob8` and counts in numpy (host
 clock per stage). Reported per mode: the pass, its ratio to K x the `none` pass of the same run, the summed time
 of the TTA-only kernels, their share of the pass and the bytes they move per second (bytes from the shapes).
+With `--regions` the tool times region analysis instead (`... --regions > profiles/predict_regions.txt`,
+`... --regions --fp32_path split >> profiles/predict_regions.txt`): (R) the stages of one labelling, its table and one
+apply around HIP events (local, seam, flatten, the torch compaction of the roots, stats, apply), with the bytes they
+move from the shapes, on the network's own mask and on adversarial masks (a serpentine and a full plane: one region
+over every seam; noise at p = 0.59 and specks: very many); (P) `predict_image` with and without
+`regions=True, min_region, fill_holes`, alternating, host clock; (H) the same tail done on the host with
+scipy.ndimage and numpy on the planes of the same run, and whether both give the same mask and table.
 One warm-up pass, then `rounds` passes of (A) and (B) alternating; the median pass is reported with the
 min-max spread. Before timing, (A)'s mask is checked against the thresholds applied to its own planes, and
 (B)'s host mask against it away from the seams. Nothing here is a threshold: the tool records times.
@@ -312,6 +319,201 @@ def tta_report(a, net, image, plan, t_out, t_sel, dev, mpix):
     return 0 if ok else 1
 
 
+# ----------------------------------------------------------------------------- --regions
+REGION_STAGES = ("local", "seam", "flatten", "roots to rows (torch)", "stats", "action (torch)", "apply")
+
+
+def region_bytes(H, W):
+    """Algorithmic bytes per stage, from the shapes: mask 1 B, parent / label 4 B, root flag 1 B, prob8 1 B a pixel;
+    the seam pass touches about three 4-B words per pixel of the tile borders."""
+    px, seam = H * W, (-(-H // 64) - 1) * W + (-(-W // 64) - 1) * H
+    return {"local": px * (1 + 4), "seam": seam * 3 * 4, "flatten": px * (4 + 4 + 1), "stats": px * (4 + 1 + 1),
+            "apply": px * (1 + 4 + 1)}
+
+
+def region_stages(mask, prob8, value, connectivity, min_region):
+    """One labelling of `mask`, its table, and one apply (regions below min_region -> 0, on a copy) with an event
+    after every stage: ({stage: ms}, Regions, error word)."""
+    from selectivenet_for_semantic_segmentation_binary_amd import _lib as K
+
+    ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
+    H, W = mask.shape
+    lp, dev = -(-W // 4) * 4, mask.device
+    parent = torch.empty(H, lp, dtype=torch.int32, device=dev)
+    labels = torch.empty(H, lp, dtype=torch.int32, device=dev)
+    roots = torch.empty(H, lp, dtype=torch.uint8, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    work, counts = mask.clone(), torch.zeros(4, dtype=torch.int64, device=dev)
+    e = [ev() for _ in range(len(REGION_STAGES) + 1)]
+    e[0].record()
+    for i, passes in enumerate((1, 2, 4)):
+        K.call("selunet_regions_label", K.ptr(mask), mask.stride(0), H, W, value, connectivity, K.ptr(parent),
+               K.ptr(labels), K.ptr(roots), lp, K.ptr(err), passes, K.stream_ptr())
+        e[i + 1].record()
+    pos = torch.nonzero(roots.view(-1)).view(-1)
+    parent.view(-1)[pos] = torch.arange(pos.numel(), dtype=torch.int32, device=dev)
+    lab = PR._Labelling(H, W, lp, labels, parent, lp, 1 + torch.div(pos, lp, rounding_mode="floor") * W + pos % lp, err)
+    e[4].record()
+    reg = PR._table("predict_bench", mask, lab, prob8)
+    e[5].record()
+    action = (reg.area < min_region).to(torch.uint8)
+    e[6].record()
+    if lab.n:
+        PR._apply("predict_bench", work, lab, action, counts)
+    e[7].record()
+    torch.cuda.synchronize()
+    return {k: e[i].elapsed_time(e[i + 1]) for i, k in enumerate(REGION_STAGES)}, reg, int(err.item())
+
+
+def host_regions(mask_t, prob_t, min_region, fill_holes):
+    """What a user does without the feature: mask and prob8 to the host, scipy.ndimage for the labels and the
+    table, the two clean-up steps in numpy. ({stage: ms}, final mask, table {column: int64 [n]} by canonical label)."""
+    from scipy import ndimage
+
+    ms = dict.fromkeys(("planes to host", "ndimage.label x 3", "tables (find_objects / sum / minimum)", "clean-up (numpy)"), 0.0)
+
+    def lap(name, t):
+        torch.cuda.synchronize()
+        now = time.perf_counter()
+        ms[name] += (now - t) * 1e3
+        return now
+
+    def table(mask, lab, n, prob8=None, full=True):
+        idx = np.arange(1, n + 1)
+        H, W = mask.shape
+        box = ndimage.find_objects(lab)
+        t = {"area": np.bincount(lab.ravel(), minlength=n + 1)[1:].astype(np.int64),
+             "y_min": np.array([b[0].start for b in box], np.int64), "x_min": np.array([b[1].start for b in box], np.int64),
+             "y_max": np.array([b[0].stop - 1 for b in box], np.int64), "x_max": np.array([b[1].stop - 1 for b in box], np.int64)}
+        ab = np.pad(mask == 127, 1)
+        near = ab[:-2, 1:-1].astype(np.uint8) + ab[2:, 1:-1] + ab[1:-1, :-2] + ab[1:-1, 2:]
+        t["abstain_contacts"] = np.asarray(ndimage.sum(near, lab, idx)).astype(np.int64).reshape(n)
+        if full:  # sums of coordinates below 2^53: exact in the float64 that ndimage.sum returns
+            yy, xx = np.indices((H, W), dtype=np.int32, sparse=True)
+            t["sum_y"] = np.asarray(ndimage.sum(np.broadcast_to(yy, (H, W)), lab, idx)).astype(np.int64).reshape(n)
+            t["sum_x"] = np.asarray(ndimage.sum(np.broadcast_to(xx, (H, W)), lab, idx)).astype(np.int64).reshape(n)
+            t["prob_sum"] = np.asarray(ndimage.sum(prob8, lab, idx)).astype(np.int64).reshape(n)
+            first = np.asarray(ndimage.minimum(np.arange(H * W, dtype=np.int64).reshape(H, W), lab, idx)).reshape(n)
+            t["label"] = 1 + first.astype(np.int64)
+        return t
+
+    t_all = t = time.perf_counter()
+    mask, prob8 = mask_t.cpu().numpy().copy(), prob_t.cpu().numpy()
+    t = lap("planes to host", t)
+    eight = np.ones((3, 3), int)
+    if min_region > 0:
+        lab, n = ndimage.label(mask == 255, structure=eight)
+        t = lap("ndimage.label x 3", t)
+        tb = table(mask, lab, n, full=False)
+        t = lap("tables (find_objects / sum / minimum)", t)
+        mask[np.concatenate([[False], tb["area"] < min_region])[lab]] = 0
+        t = lap("clean-up (numpy)", t)
+    if fill_holes > 0:
+        H, W = mask.shape
+        lab, n = ndimage.label(mask == 0)
+        t = lap("ndimage.label x 3", t)
+        tb = table(mask, lab, n, full=False)
+        t = lap("tables (find_objects / sum / minimum)", t)
+        hole = ((tb["y_min"] > 0) & (tb["x_min"] > 0) & (tb["y_max"] < H - 1) & (tb["x_max"] < W - 1)
+                & (tb["abstain_contacts"] == 0) & (tb["area"] <= fill_holes))
+        mask[np.concatenate([[False], hole])[lab]] = 255
+        t = lap("clean-up (numpy)", t)
+    lab, n = ndimage.label(mask == 255, structure=eight)
+    t = lap("ndimage.label x 3", t)
+    tb = table(mask, lab, n, prob8)
+    order = np.argsort(tb["label"])
+    tb = {k: v[order] for k, v in tb.items()}
+    t = lap("tables (find_objects / sum / minimum)", t)
+    ms["whole tail"] = (time.perf_counter() - t_all) * 1e3
+    return ms, mask, tb
+
+
+def regions_report(a, net, image, plan, t_out, t_sel, dev, mpix):
+    """--regions: per-stage times on the network's own mask and on two adversarial masks; the clean-up's share of a
+    pass, alternating with the plain pass; and the host-side alternative on the same planes."""
+    H = W = a.size
+    kw = dict(tile=a.tile, halo=a.halo, batch_size=a.batch)
+    clean = dict(min_region=a.min_region, fill_holes=a.fill_holes)
+    plain = PR.predict_image(net, image, **kw)
+    serp = np.zeros((H, W), np.uint8)
+    serp[0::2] = 255
+    for k, y in enumerate(range(1, H - 1, 2)):
+        serp[y, W - 1 if k % 2 == 0 else 0] = 255
+    noise = ((np.random.Generator(np.random.PCG64(59)).random((H, W)) < 0.59) * 255).astype(np.uint8)
+    speck = ((np.random.Generator(np.random.PCG64(5)).random((H, W)) < 0.05) * 255).astype(np.uint8)
+    masks = [("the network's mask, 8-connected", plain.mask, 8),
+             ("serpentine over the whole image (one region), 4-connected", torch.from_numpy(serp).to(dev), 4),
+             ("all 255 (one region), 8-connected", torch.full((H, W), 255, dtype=torch.uint8, device=dev), 8),
+             ("noise p = 0.59, 4-connected", torch.from_numpy(noise).to(dev), 4),
+             ("specks p = 0.05, 8-connected", torch.from_numpy(speck).to(dev), 8)]
+    by = region_bytes(H, W)
+
+    def row(rows, k):
+        v = [t[k] for t in rows]
+        return statistics.median(v), f"{statistics.median(v):10.3f} [{min(v):.3f} .. {max(v):.3f}]"
+
+    ok = True
+    for name, m, conn in masks:
+        region_stages(m, plain.prob8, 255, conn, a.min_region)  # warm-up
+        runs = [region_stages(m, plain.prob8, 255, conn, a.min_region) for _ in range(a.rounds)]
+        reg = runs[0][1]
+        ok = ok and all(r[2] == 0 for r in runs)
+        big = int(reg.area.max().item()) if len(reg) else 0
+        print(f"(R) stages on {name}: {len(reg)} regions, the largest of {big} pixels; error word {runs[0][2]}")
+        total = 0.0
+        for k in REGION_STAGES:
+            med, s = row([r[0] for r in runs], k)
+            total += med
+            gbs = f"  {by[k] / 1e6:8.1f} MB, {by[k] / med / 1e6:7.1f} GB/s" if k in by and med > 0 else ""
+            print(f"    {k:<24}{s}{gbs}")
+        print(f"    {'sum of the stages':<24}{total:10.3f}")
+    # ---- clean_mask as predict_image runs it (three labellings, their tables, two applies, the counts), HIP events
+    tc = []
+    for _ in range(a.rounds + 1):
+        work = plain.mask.clone()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        PR.clean_mask(work, plain.prob8, **clean)
+        e1.record()
+        torch.cuda.synchronize()
+        tc.append(e0.elapsed_time(e1))
+    tc = tc[1:]
+    print(f"(R) clean_mask(min_region={a.min_region}, fill_holes={a.fill_holes}) on the network's mask, first call to the "
+          f"one read: {statistics.median(tc):10.3f} [{min(tc):.3f} .. {max(tc):.3f}]")
+    # ---- the share of a pass: plain and with the clean-up, alternating, host clock around a synchronise
+    def timed(**extra):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        pred = PR.predict_image(net, image, **kw, **extra)
+        pred.mask.cpu(), pred.prob8.cpu()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) * 1e3, pred
+
+    timed(regions=True, **clean)
+    tp, tr, th = [], [], []
+    for _ in range(a.rounds):
+        tp.append(timed()[0])
+        ms, pred = timed(regions=True, **clean)
+        tr.append(ms)
+        th.append(host_regions(plain.mask, plain.prob8, a.min_region, a.fill_holes)[0])
+    mp, mr = statistics.median(tp), statistics.median(tr)
+    print(f"(P) predict_image + mask and prob8 to the host, plain:        {mp:10.2f} [{min(tp):.2f} .. {max(tp):.2f}]")
+    print(f"(P) the same with regions=True, min_region={a.min_region}, fill_holes={a.fill_holes}: {mr:10.2f} "
+          f"[{min(tr):.2f} .. {max(tr):.2f}]: + {mr - mp:.2f} ms = {(mr - mp) / mp:.4f} of the plain pass; "
+          f"{len(pred.regions)} regions, {pred.cleanup}")
+    print("(H) the same tail on the host: planes to the host, scipy.ndimage, numpy (host clock per stage)")
+    for k in th[0]:
+        print(f"    {k:<40}{row(th, k)[1]}")
+    print(f"    (H) whole tail / (P) added time = {row(th, 'whole tail')[0] / max(mr - mp, 1e-9):.1f}")
+    _, host_mask, host_table = host_regions(plain.mask, plain.prob8, a.min_region, a.fill_holes)
+    dev_table = pred.regions.numpy()
+    same = bool(np.array_equal(host_mask, pred.mask.cpu().numpy())) and \
+        all(np.array_equal(dev_table[c], host_table[c]) for c in PR.REGION_COLUMNS)
+    print(f"(H) host mask and table equal the device's, every column: {same}")
+    print("checks passed:", ok and same)
+    return 0 if ok and same else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=4096)
@@ -322,6 +524,9 @@ def main():
     ap.add_argument("--compute_dtype", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--fp32_path", default="exact", choices=["exact", "split"])
     ap.add_argument("--tta", action="store_true", help="time test-time augmentation: none, flips, d4 and d4 on the host")
+    ap.add_argument("--regions", action="store_true", help="time region labelling, the table and the clean-up")
+    ap.add_argument("--min_region", type=int, default=64)
+    ap.add_argument("--fill_holes", type=int, default=64)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("predict_bench: no GPU visible (timings are taken on the device only)")
@@ -348,6 +553,8 @@ def main():
     print(f"(A) {plan!r}: {plan.n} tiles in {-(-plan.n // a.batch)} batches")
     if a.tta:
         return tta_report(a, net, image, plan, t_out, t_sel, dev, mpix)
+    if a.regions:
+        return regions_report(a, net, image, plan, t_out, t_sel, dev, mpix)
     n_old = (a.size // a.tile) ** 2
     print(f"(B) {n_old} patches of {a.tile} x {a.tile} without halo in {-(-n_old // a.batch)} batches")
 
