@@ -851,6 +851,32 @@ int selunet_regions_apply(uint8_t* mask, int64_t mask_pitch, int32_t H, int32_t 
                           int32_t lp, const int32_t* rowidx, int32_t rp, const uint8_t* action,
                           int64_t n_rows, unsigned long long* counts, void* stream);
 
+/* ---- tissue mask of whole-image prediction -------------------------------------
+ * Bare glass is told from tissue per pixel by an exact integer rule, so that tiles whose whole input window
+ * is glass need not be forwarded. A tissue plane is uint8, 0 for glass and anything else (255 as written
+ * here) for tissue. Integer arithmetic only: every result is the same bit for bit on every run. */
+/* img: uint8 [H][W][3] RGB on the device -> plane: uint8 [H][pitch]. A pixel is glass iff
+ * min(r,g,b) >= bright and max(r,g,b) - min(r,g,b) <= spread; plane = 0 for glass, 255 for every other
+ * pixel, 0 in the bytes x >= W of a row. EINVAL: a null pointer; H or W outside [1, 65535]; bright or spread
+ * outside [0, 255]; pitch < W or pitch % 4 != 0; plane not 4-B aligned. */
+int selunet_tissue_plane(const uint8_t* img, int32_t H, int32_t W, int32_t bright, int32_t spread,
+                         uint8_t* plane, int32_t pitch, void* stream);
+/* counts: int32 [n], caller-zeroed, counts[i] += the number of positions (y, x) of tile i's th x tw window
+ * whose source pixel is tissue; the source pixel is selunet_tile_gather_flip's for `flip`: row
+ * fy(refl(y0 + y, H)), column fx(refl(x0 + x, W)) of plane (rows of `pitch` bytes), so a reflected copy of a
+ * pixel counts again. origins: DEVICE int32 [n][2] as selunet_tile_gather's. Integer atomics only.
+ * EINVAL: a null pointer; the size and tile rules of selunet_tile_gather; pitch < W; flip outside [0, 3];
+ * th * tw >= 2^31; counts not 4-B aligned. */
+int selunet_tile_tissue_counts(const uint8_t* plane, int64_t pitch, int32_t H, int32_t W,
+                               const int32_t* origins, int32_t n, int32_t th, int32_t tw, int32_t flip,
+                               int32_t* counts, void* stream);
+/* counts: uint64 [4], caller-zeroed, += {pixels equal to 0, to 255, to 127, their sum} of mask (uint8 rows of
+ * mask_pitch bytes, at any alignment) over the pixels y < H, x < W that are tissue in plane (rows of `pitch`
+ * bytes). Integer atomics only. EINVAL: a null pointer; H or W outside [1, 65535]; a pitch below W; counts
+ * not 8-B aligned. */
+int selunet_tissue_class_counts(const uint8_t* mask, int64_t mask_pitch, const uint8_t* plane, int64_t pitch,
+                                int32_t H, int32_t W, unsigned long long* counts, void* stream);
+
 /* ---- multi-GPU overlap probe (bench/tools only, not on the training path) ------
  * Stand-in for one bucketed RCCL all-reduce kernel on a single GPU: n_wg workgroups of 256 threads
  * reduce-copy dst[i] += src[i] over their slices of [0, n) (n % 4 == 0, 16-B aligned), repeatedly,

@@ -16,6 +16,8 @@ Drop-in replacements for the reference's hot path (yellofi/SelectiveNet_for_sema
                                         optionally averaged over the image's flips / D4 orientations (tta=)
 * `label_regions`, `region_table`,       connected regions of a prediction mask, their exact table and the
   `clean_mask`                           small-region / hole clean-up, on the device (predict_image(regions=...))
+* `tissue_plane`                         the glass / tissue mask of an image; predict_image(tissue=True) does not
+                                        forward tiles without tissue and counts tumor over tissue
 * `parallel.init_data_parallel`        <- torch.nn.DataParallel (train.py:131-134)
 
 All compute runs in libselunet.so (HIP, gfx950); there is no CPU fallback.
@@ -24,7 +26,7 @@ from .layout import count_params, state_dict_keys  # noqa: F401
 from .metrics import PatchReport, SelectiveSweep  # noqa: F401
 from .model import CBR_2D, UNet, UNet_B  # noqa: F401
 from .optim import Adam  # noqa: F401
-from .predict import TilePlan, clean_mask, label_regions, predict_image, region_table  # noqa: F401
+from .predict import TilePlan, clean_mask, label_regions, predict_image, region_table, tissue_plane  # noqa: F401
 from .selective_loss import (BCEWithLogitsLoss, CrossEntropyLoss, calc_selective_risk_image,  # noqa: F401
                              calc_selective_risk_image_b)
 from . import parallel  # noqa: F401

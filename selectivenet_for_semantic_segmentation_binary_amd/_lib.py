@@ -211,6 +211,9 @@ SIGNATURES = {
     "selunet_regions_stats": (c_int32, [P, c_int32, P, c_int64, P, c_int64, c_int32, c_int32, P, c_int32, c_int64, P,
                                         P]),
     "selunet_regions_apply": (c_int32, [P, c_int64, c_int32, c_int32, P, c_int32, P, c_int32, P, c_int64, P, P]),
+    "selunet_tissue_plane": (c_int32, [P, c_int32, c_int32, c_int32, c_int32, P, c_int32, P]),
+    "selunet_tile_tissue_counts": (c_int32, [P, c_int64, c_int32, c_int32, P, c_int32, c_int32, c_int32, c_int32, P, P]),
+    "selunet_tissue_class_counts": (c_int32, [P, c_int64, P, c_int64, c_int32, c_int32, P, P]),
     "selunet_set_option": (c_int64, [c_int32, c_int64]),
     "selunet_cu_hold": (c_int32, [P, P, c_int64, c_int32, c_float, P]),
 }

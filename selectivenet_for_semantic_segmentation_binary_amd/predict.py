@@ -30,6 +30,13 @@ than N pixels, fill enclosed background holes of at most M pixels that touch no 
 regions of the cleaned mask: `<stem>_mask.png` is then the cleaned mask, `<stem>_regions.csv` holds one row per region
 (exact integer columns plus centroid and mean probability), and the image's predict.json entry gains "regions",
 "largest_region_area" and "cleanup". Without these flags nothing of that runs and every file is as before.
+
+`--tissue 1`, `--tissue_bright B`, `--tissue_spread S`, `--tissue_min_pixels N` (`predict_image(..., tissue=, tissue_bright=,
+tissue_spread=, tissue_min_pixels=)`) mark bare glass on the device (a pixel is glass iff min(r,g,b) >= B
+and max - min <= S) and do not forward a tile whose input window holds fewer than N tissue pixels: its core is background,
+selected, with logit -inf and prob8 0. `<stem>_tissue.png` (L: 255 tissue, 0 glass) is written, the image's predict.json
+entry gains "tissue_pixels", "tissue_counts", "tumor_fraction_of_tissue", "tiles_forwarded" and "tiles_total", and the
+document's head the rule's three numbers. Without `--tissue 1` nothing of that runs and every file is as before.
 """
 from __future__ import annotations
 
@@ -257,6 +264,71 @@ def tta_finalize(a, b, members: int, H: int, W: int, t_out: float, t_sel: float,
            0 if b[0] is None else b[0].shape[1], t_out, t_sel, K.ptr(logit), K.ptr(selection), K.ptr(mask),
            K.ptr(prob), K.ptr(votes), K.ptr(sel_votes), K.ptr(counts), K.stream_ptr())
     return (logit, selection, mask, prob, votes, sel_votes), counts
+
+
+# ----------------------------------------------------------------------------- tissue
+# The reference's glass model paints 0.96 + 0.005 N(0,1) per channel (utils/data_utils.py:127-157); the defaults
+# are that model at six standard deviations: bright = floor(255 (0.96 - 6 * 0.005)), spread = ceil(255 * 6 *
+# sqrt(2) * 0.005) (the difference of two channels has sqrt(2) times a channel's deviation).
+TISSUE_BRIGHT = 237
+TISSUE_SPREAD = 11
+
+
+def _tissue_args(fn, bright, spread, min_pixels):
+    for name, v in (("tissue_bright", bright), ("tissue_spread", spread)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= v <= 255:
+            raise ValueError(f"{fn}: {name} must be an integer in [0, 255] (got {v!r})")
+    if not isinstance(min_pixels, (int, np.integer)) or isinstance(min_pixels, bool) or min_pixels < 1:
+        raise ValueError(f"{fn}: tissue_min_pixels must be an integer >= 1 (got {min_pixels!r})")
+
+
+def tissue_plane(image_u8: torch.Tensor, bright: int = TISSUE_BRIGHT, spread: int = TISSUE_SPREAD) -> torch.Tensor:
+    """`selunet_tissue_plane`: image uint8 [H,W,3] on the GPU -> uint8 [H,W], 255 tissue / 0 glass (glass iff
+    min(r,g,b) >= bright and max - min <= spread): a view of a plane whose rows are padded to a multiple of 4."""
+    _check("tissue_plane: image", image_u8, torch.uint8)
+    if image_u8.dim() != 3 or image_u8.shape[2] != 3:
+        raise ValueError(f"tissue_plane: image must be RGB [H,W,3] uint8 (got {tuple(image_u8.shape)})")
+    H, W = int(image_u8.shape[0]), int(image_u8.shape[1])
+    pitch = -(-W // 4) * 4
+    plane = torch.empty(H, pitch, dtype=torch.uint8, device=image_u8.device)
+    K.call("selunet_tissue_plane", K.ptr(image_u8), H, W, int(bright), int(spread), K.ptr(plane), pitch, K.stream_ptr())
+    return plane[:, :W]
+
+
+def tile_tissue_counts(plane: torch.Tensor, origins: torch.Tensor, th: int, tw: int, flip: int = 0,
+                       out: torch.Tensor | None = None) -> torch.Tensor:
+    """`selunet_tile_tissue_counts`: plane uint8 [H,W] (tissue_plane's view, or any with contiguous rows) and
+    origins int32 [n,2] -> int32 [n] (into `out` when given), the tissue pixels of each tile's th x tw window of
+    the plane flipped by `flip` and continued by reflection: what `tile_gather_flip` would gather."""
+    pitch = _plane("tile_tissue_counts", "plane", plane, torch.uint8)
+    _check("tile_tissue_counts: origins", origins, torch.int32)
+    if origins.dim() != 2 or origins.shape[1] != 2:
+        raise ValueError(f"tile_tissue_counts: origins must be [n,2] (got {tuple(origins.shape)})")
+    n = origins.shape[0]
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=plane.device)
+    _check("tile_tissue_counts: out", out, torch.int32)
+    if tuple(out.shape) != (n,):
+        raise ValueError(f"tile_tissue_counts: out must be [{n}] (got {tuple(out.shape)})")
+    out.zero_()  # the kernel adds
+    K.call("selunet_tile_tissue_counts", K.ptr(plane), pitch, plane.shape[0], plane.shape[1], K.ptr(origins), n, th, tw,
+           int(flip), K.ptr(out), K.stream_ptr())
+    return out
+
+
+def tissue_class_counts(mask: torch.Tensor, plane: torch.Tensor, counts: torch.Tensor | None = None) -> torch.Tensor:
+    """`selunet_tissue_class_counts`: int64 [4] on the device, {background, tumor, abstained, pixels} of the
+    0 / 255 / 127 mask [H,W] over the tissue pixels of plane [H,W] (added into `counts` when given)."""
+    mp = _plane("tissue_class_counts", "mask", mask, torch.uint8)
+    pp = _plane("tissue_class_counts", "plane", plane, torch.uint8, int(mask.shape[0]), int(mask.shape[1]))
+    if counts is None:
+        counts = torch.zeros(4, dtype=torch.int64, device=mask.device)  # uint64 bits
+    _check("tissue_class_counts: counts", counts, torch.int64)
+    if counts.numel() != 4:
+        raise ValueError("tissue_class_counts: counts must hold 4 words")
+    K.call("selunet_tissue_class_counts", K.ptr(mask), mp, K.ptr(plane), pp, mask.shape[0], mask.shape[1], K.ptr(counts),
+           K.stream_ptr())
+    return counts
 
 
 # ----------------------------------------------------------------------------- regions (DESIGN.md §7h)
@@ -497,6 +569,14 @@ class Prediction:
     members: int = 1
     regions: Regions | None = None  # with region analysis: the tumor regions of the final mask
     cleanup: dict | None = None     # and {removed_regions, removed_pixels, filled_holes, filled_pixels}
+    # with tissue=True, else None: the tissue plane (uint8 [H,W] device view, 255 tissue / 0 glass),
+    # `counts` over the tissue pixels only, per member a bool array over its plan's tiles (True: forwarded), and
+    # the forwarded and all tiles summed over the members
+    tissue: torch.Tensor | None = None
+    tissue_counts: np.ndarray | None = None
+    tiles_kept: list | None = None
+    tiles_forwarded: int | None = None
+    tiles_total: int | None = None
 
     @property
     def unanimous_fraction(self) -> float | None:
@@ -517,21 +597,68 @@ class Prediction:
         sel = int(self.counts[0] + self.counts[1])
         return float(self.counts[1]) / sel if sel else float("nan")
 
+    @property
+    def tumor_fraction_of_tissue(self) -> float | None:
+        """The share of tumor among the selected tissue pixels (NaN when there are none); None without tissue."""
+        if self.tissue_counts is None:
+            return None
+        sel = int(self.tissue_counts[0] + self.tissue_counts[1])
+        return float(self.tissue_counts[1]) / sel if sel else float("nan")
+
+
+class _Skipped:
+    """The output of a tile that is not forwarded: out = -inf and, with a selection head,
+    sel = +inf, so that the existing stitch / accumulate write background, selected, prob8 0 and no tumor vote.
+    One pair of constant buffers of up to `batch_size` tiles, made when the first tile is skipped."""
+
+    def __init__(self, batch_size, tile, selective, device):
+        self.shape, self.selective, self.device = (batch_size, tile, tile), selective, device
+        self.out = self.sel = None
+
+    def batches(self, origins_host, keep):
+        """(out, sel, host origins, device origins) per batch of the tiles with keep False."""
+        oh = np.ascontiguousarray(origins_host[~keep])
+        if not len(oh):
+            return
+        if self.out is None:
+            self.out = torch.full(self.shape, float("-inf"), dtype=torch.float32, device=self.device)
+            self.sel = torch.full(self.shape, float("inf"), dtype=torch.float32, device=self.device) if self.selective else None
+        od = torch.from_numpy(oh).to(self.device)
+        for a in range(0, len(oh), self.shape[0]):
+            b = min(a + self.shape[0], len(oh))
+            yield self.out[:b - a], None if self.sel is None else self.sel[:b - a], oh[a:b], od[a:b]
+
+
+def _kept_origins(origins_host, origins, keep):
+    """The host and device origins of the tiles to forward: the plan's own when every tile is kept."""
+    if keep is None or keep.all():
+        return origins_host, origins
+    oh = np.ascontiguousarray(origins_host[keep])
+    return oh, torch.from_numpy(oh).to(origins.device)
+
 
 def predict_image(net, image_u8, *, tile: int = 512, halo: int = HALO_MIN, batch_size: int = 16,
                   cut_off: float = 0.5, s_cut_off: float = 0.5, single_scale: str = "sigmoid",
                   input_type: str = "RGB", prob8: bool = True, allow_small_halo: bool = False,
                   tta: str = "none", regions: bool = False, min_region: int = 0, fill_holes: int = 0,
-                  connectivity: int = 8) -> Prediction:
+                  connectivity: int = 8, tissue: bool = False, tissue_bright: int = TISSUE_BRIGHT,
+                  tissue_spread: int = TISSUE_SPREAD, tissue_min_pixels: int = 1) -> Prediction:
     """Apply `net` (a UNet_B on a cuda device, in eval mode) to `image_u8`, a numpy or torch uint8 [H,W,3] RGB
     image of any size: gather -> net -> stitch per batch of `batch_size` tiles, on the current stream.
     tta: "none", or "flips" / "d4": the mean over the 4 flips / the 8 flips and transposes of the image
     (`TTA_MEMBERS`), with the votes of the members.
     regions / min_region / fill_holes / connectivity: with `regions` or a clean-up size > 0 the
     mask is cleaned in place (`clean_mask`), counts are those of the cleaned mask, and `regions` / `cleanup`
-    hold the table of its tumor regions and what the clean-up did; with the defaults nothing of that runs."""
+    hold the table of its tumor regions and what the clean-up did; with the defaults nothing of that runs.
+    tissue / tissue_bright / tissue_spread / tissue_min_pixels: with `tissue` a pixel is glass iff
+    min(r,g,b) >= tissue_bright and max - min <= tissue_spread, and a tile whose input window holds fewer than
+    tissue_min_pixels tissue pixels is not forwarded: its core is background, selected, logit -inf (selection
+    +inf), prob8 0. The result gains tissue, tissue_counts, tiles_kept, tiles_forwarded and tiles_total; with the
+    default nothing of that runs."""
     if tta not in TTA_MEMBERS:
         raise ValueError(f"predict_image: tta {tta!r}: one of {', '.join(map(repr, TTA_MEMBERS))}")
+    _tissue_args("predict_image", tissue_bright, tissue_spread, tissue_min_pixels)
+    rule = (int(tissue_bright), int(tissue_spread), int(tissue_min_pixels)) if tissue else None
     if net.training:
         raise RuntimeError("predict_image needs the network in eval mode (net.eval()): tiling is exact only with "
                            "the running BatchNorm statistics")
@@ -557,74 +684,128 @@ def predict_image(net, image_u8, *, tile: int = 512, halo: int = HALO_MIN, batch
     if analyse:
         pred = predict_image(net, img, tile=tile, halo=halo, batch_size=batch_size, cut_off=cut_off,
                              s_cut_off=s_cut_off, single_scale=single_scale, input_type=input_type, prob8=prob8,
-                             allow_small_halo=allow_small_halo, tta=tta)
+                             allow_small_halo=allow_small_halo, tta=tta, tissue=tissue, tissue_bright=tissue_bright,
+                             tissue_spread=tissue_spread, tissue_min_pixels=tissue_min_pixels)
         with torch.cuda.device(device):  # the stages read the mask and prob8 only: any forward path, any tta
             pred.regions, pred.counts, *done = clean_mask(pred.mask, pred.prob8, int(min_region), int(fill_holes),
                                                           connectivity)
+            if rule:  # the tissue counts are those of the cleaned mask
+                pred.tissue_counts = tissue_class_counts(pred.mask, pred.tissue).cpu().numpy().astype(np.int64)
         pred.cleanup = dict(zip(CLEANUP_NAMES, done))
         return pred
     if tta != "none":
         return _predict_tta(net, img, device, plan, TTA_MEMBERS[tta], batch_size, t_out, t_sel, input_type, prob8,
-                            allow_small_halo)
+                            allow_small_halo, rule)
     with torch.cuda.device(device), torch.no_grad():
         img = img.to(device).contiguous()  # the one upload
         origins = torch.from_numpy(plan.origins).to(device)
+        keep = glass = None
+        if rule:
+            glass = tissue_plane(img, rule[0], rule[1])
+            # the one read before the first forward
+            keep = tile_tissue_counts(glass, origins, tile, tile).cpu().numpy() >= rule[2]
         # the cores cover the canvases exactly once: no initial value is read
         logit = torch.empty(plan.Hc, plan.Wc, dtype=torch.float32, device=device)
         selection = torch.empty_like(logit) if selective else None
         mask = torch.empty(plan.Hc, plan.Wc, dtype=torch.uint8, device=device)
         prob = torch.empty_like(mask) if prob8 else None
-        counts = torch.zeros(4, dtype=torch.int64, device=device)  # uint64 bits
+        counts = torch.zeros(8 if rule else 4, dtype=torch.int64, device=device)  # uint64 bits
+        image_counts = counts[:4] if rule else counts
+        run_host, run = _kept_origins(plan.origins, origins, keep)  # the plan's own without a tissue rule
+        n_run = len(run_host)
         x_buf = torch.empty(min(batch_size, plan.n), _CIN[input_type], tile, tile, dtype=torch.float32, device=device)
-        for a in range(0, plan.n, batch_size):
-            b = min(a + batch_size, plan.n)  # the last batch is run as ragged as it is
-            x = tile_gather(img, origins[a:b], tile, tile, input_type, out=x_buf[:b - a])
+        for a in range(0, n_run, batch_size):
+            b = min(a + batch_size, n_run)  # the last batch is run as ragged as it is
+            x = tile_gather(img, run[a:b], tile, tile, input_type, out=x_buf[:b - a])
             res = net(x)
             out, sel = (res[0], res[1]) if selective else (res, None)
-            tile_stitch(out.contiguous(), None if sel is None else sel.contiguous(), plan.origins[a:b], origins[a:b],
-                        halo, H, W, t_out, t_sel, logit, selection, mask, prob, counts)
+            tile_stitch(out.contiguous(), None if sel is None else sel.contiguous(), run_host[a:b], run[a:b],
+                        halo, H, W, t_out, t_sel, logit, selection, mask, prob, image_counts)
+        if rule:
+            skipped = _Skipped(min(batch_size, plan.n), tile, selective, device)
+            for out, sel, oh, od in skipped.batches(plan.origins, keep):
+                tile_stitch(out, sel, oh, od, halo, H, W, t_out, t_sel, logit, selection, mask, prob, image_counts)
+            tissue_class_counts(mask[:H, :W], glass, counts[4:])
         host_counts = counts.cpu().numpy().astype(np.int64)  # the one read
-    return Prediction(logit[:H, :W], None if selection is None else selection[:H, :W], mask[:H, :W],
-                      None if prob is None else prob[:H, :W], host_counts, plan)
+    pred = Prediction(logit[:H, :W], None if selection is None else selection[:H, :W], mask[:H, :W],
+                      None if prob is None else prob[:H, :W], host_counts[:4], plan)
+    if rule:
+        pred.tissue, pred.tissue_counts, pred.tiles_kept = glass, host_counts[4:], [keep]
+        pred.tiles_forwarded, pred.tiles_total = int(keep.sum()), plan.n
+    return pred
 
 
-def _predict_tta(net, img, device, plan, members, batch_size, t_out, t_sel, input_type, prob8, allow_small_halo):
+def _predict_tta(net, img, device, plan, members, batch_size, t_out, t_sel, input_type, prob8, allow_small_halo,
+                 rule=None):
     """predict_image with test-time augmentation. Member k = 4 c + f is the prediction of the
     image of orientation class c (0: the image; 1: its transpose, formed once on the device) flipped by f
     (bit 1 rows, bit 0 columns), mapped back. Per class, members run one after another: flipped gather -> net
     -> accumulate per batch of tiles into the class's fp32 sums and vote planes, whose rows are padded to a
-    multiple of 8 pixels (zeros, never written); one finalize forms the mean and everything derived from it."""
+    multiple of 8 pixels (zeros, never written); one finalize forms the mean and everything derived from it.
+    rule = (bright, spread, min_pixels): every member skips the tiles of its own tiling whose
+    window holds fewer than min_pixels tissue pixels; the window counts of all members are read at once before
+    the first forward, and a skipped core is accumulated as -inf (selection +inf)."""
     H, W, tile, halo = plan.H, plan.W, plan.tile, plan.halo
     selective = bool(net.selective)
     with torch.cuda.device(device), torch.no_grad():
         img = img.to(device).contiguous()  # the one upload
         x_buf = torch.empty(min(batch_size, plan.n), _CIN[input_type], tile, tile, dtype=torch.float32, device=device)
+        oriented = {}
+
+        def orientation(c):
+            """(image, its plan, the plan's origins on the device) of class c, made when first asked for."""
+            if c not in oriented:
+                src = image_transpose(img) if c else img
+                p = TilePlan(int(src.shape[0]), int(src.shape[1]), tile, halo, allow_small_halo) if c else plan
+                oriented[c] = (src, p, torch.from_numpy(p.origins).to(device))  # the member's own tiling
+            return oriented[c]
+
+        kept = glass = None
+        if rule:
+            glass = [tissue_plane(orientation(c)[0], rule[0], rule[1]) for c in range(members // 4)]  # per pixel
+            sizes = [orientation(k // 4)[1].n for k in range(members)]
+            window = torch.empty(sum(sizes), dtype=torch.int32, device=device)
+            for k, part in enumerate(torch.split(window, sizes)):
+                tile_tissue_counts(glass[k // 4], orientation(k // 4)[2], tile, tile, k & 3, out=part)
+            host = window.cpu().numpy() >= rule[2]  # the one read before the first forward
+            kept = np.split(host, np.cumsum(sizes)[:-1])
+            skipped = _Skipped(min(batch_size, plan.n), tile, selective, device)
         classes = []
         for c in range(members // 4):
-            src = image_transpose(img) if c else img
+            src, p, origins = orientation(c)
             h, w = int(src.shape[0]), int(src.shape[1])
-            p = TilePlan(h, w, tile, halo, allow_small_halo) if c else plan  # the member's own tiling
-            origins = torch.from_numpy(p.origins).to(device)
             ws = -(-w // 8) * 8
             sums = [torch.zeros(h, ws, dtype=torch.float32, device=device) if selective or i == 0 else None
                     for i in range(2)]
             vts = [torch.zeros(h, ws, dtype=torch.uint8, device=device) if selective or i == 0 else None
                    for i in range(2)]
             for f in range(4):
-                for a in range(0, p.n, batch_size):
-                    b = min(a + batch_size, p.n)
-                    x = tile_gather_flip(src, origins[a:b], tile, tile, input_type, f, out=x_buf[:b - a])
+                keep = kept[4 * c + f] if rule else None
+                run_host, run = _kept_origins(p.origins, origins, keep)  # the plan's own without a tissue rule
+                for a in range(0, len(run_host), batch_size):
+                    b = min(a + batch_size, len(run_host))
+                    x = tile_gather_flip(src, run[a:b], tile, tile, input_type, f, out=x_buf[:b - a])
                     res = net(x)
                     out, sel = (res[0], res[1]) if selective else (res, None)
-                    tta_accumulate(out.contiguous(), None if sel is None else sel.contiguous(), p.origins[a:b],
-                                   origins[a:b], halo, f, f == 0, h, w, p.Hc, p.Wc, t_out, t_sel, sums[0], sums[1],
+                    tta_accumulate(out.contiguous(), None if sel is None else sel.contiguous(), run_host[a:b],
+                                   run[a:b], halo, f, f == 0, h, w, p.Hc, p.Wc, t_out, t_sel, sums[0], sums[1],
                                    vts[0], vts[1])
+                if rule:
+                    for out, sel, oh, od in skipped.batches(p.origins, keep):
+                        tta_accumulate(out, sel, oh, od, halo, f, f == 0, h, w, p.Hc, p.Wc, t_out, t_sel, sums[0],
+                                       sums[1], vts[0], vts[1])
             classes.append((sums[0], sums[1], vts[0], vts[1]))
         planes, counts = tta_finalize(classes[0], classes[1] if members == 8 else None, members, H, W, t_out, t_sel,
                                       prob8)
+        if rule:
+            counts = torch.cat([counts, tissue_class_counts(planes[2][:, :W], glass[0])])
         host_counts = counts.cpu().numpy().astype(np.int64)  # the one read
     logit, selection, mask, prob, votes, sel_votes = [None if t is None else t[:, :W] for t in planes]
-    return Prediction(logit, selection, mask, prob, host_counts, plan, votes, sel_votes, members)
+    pred = Prediction(logit, selection, mask, prob, host_counts[:4], plan, votes, sel_votes, members)
+    if rule:
+        pred.tissue, pred.tissue_counts, pred.tiles_kept = glass[0], host_counts[4:], kept
+        pred.tiles_forwarded, pred.tiles_total = int(sum(k.sum() for k in kept)), int(sum(sizes))
+    return pred
 
 
 # ----------------------------------------------------------------------------- CLI
@@ -658,11 +839,23 @@ def parse_arguments(argv=None):
                         help='fill background holes of at most this many pixels inside tumor (0: off)')
     parser.add_argument('--connectivity', type=int, default=8, choices=[4, 8],
                         help='connectivity of tumor regions; holes use the complementary one')
+    # ---- tissue mask: glass tiles are not forwarded
+    parser.add_argument('--tissue', type=int, default=0, choices=[0, 1],
+                        help='1: skip tiles without tissue, write <stem>_tissue.png and the tissue counts')
+    parser.add_argument('--tissue_bright', type=int, default=TISSUE_BRIGHT,
+                        help='a pixel is glass iff min(r,g,b) >= this and max - min <= --tissue_spread')
+    parser.add_argument('--tissue_spread', type=int, default=TISSUE_SPREAD, help='see --tissue_bright')
+    parser.add_argument('--tissue_min_pixels', type=int, default=1,
+                        help='a tile is forwarded iff its input window holds at least this many tissue pixels')
     args = parser.parse_args(argv)
     if args.fp32_path == 'split' and args.compute_dtype == 'bf16':
         parser.error('--fp32_path split is an fp32 path: not with --compute_dtype bf16')
     if args.min_region < 0 or args.fill_holes < 0:
         parser.error('--min_region and --fill_holes must be >= 0')
+    if not (0 <= args.tissue_bright <= 255 and 0 <= args.tissue_spread <= 255):
+        parser.error('--tissue_bright and --tissue_spread must be in [0, 255]')
+    if args.tissue_min_pixels < 1:
+        parser.error('--tissue_min_pixels must be >= 1')
     return args
 
 
@@ -709,6 +902,12 @@ def image_record(path, pred: Prediction) -> dict:
         rec["regions"] = len(pred.regions)
         rec["largest_region_area"] = int(pred.regions.area.max().item()) if len(pred.regions) else 0
         rec["cleanup"] = {k: int(v) for k, v in pred.cleanup.items()}
+    if pred.tissue_counts is not None:  # only with the tissue mask
+        tc = [int(v) for v in pred.tissue_counts]
+        rec["tissue_pixels"] = tc[3]
+        rec["tissue_counts"] = dict(zip(COUNT_NAMES, tc))
+        rec["tumor_fraction_of_tissue"] = tc[1] / (tc[0] + tc[1]) if tc[0] + tc[1] else None
+        rec["tiles_forwarded"], rec["tiles_total"] = int(pred.tiles_forwarded), int(pred.tiles_total)
     return rec
 
 
@@ -753,12 +952,18 @@ def predict_files(args) -> dict:
     doc = {"checkpoint": ckpt, "selective": bool(args.selective), "input_type": args.input_type,
            "cut_off": args.cut_off, "s_cut_off": args.s_cut_off, "single_scale": args.single_scale, "tta": args.tta,
            "images": []}
+    if args.tissue:  # only with the tissue mask: a plain run's file is what it was
+        doc.update(tissue_bright=args.tissue_bright, tissue_spread=args.tissue_spread,
+                   tissue_min_pixels=args.tissue_min_pixels)
+        doc["images"] = doc.pop("images")  # the list stays last
     for path in files:
         image = np.array(Image.open(path).convert("RGB"))
         pred = predict_image(net, image, tile=args.tile, halo=args.halo, batch_size=args.batch_size,
                              cut_off=args.cut_off, s_cut_off=args.s_cut_off, single_scale=args.single_scale,
                              input_type=args.input_type, tta=args.tta, regions=bool(args.regions),
-                             min_region=args.min_region, fill_holes=args.fill_holes, connectivity=args.connectivity)
+                             min_region=args.min_region, fill_holes=args.fill_holes, connectivity=args.connectivity,
+                             tissue=bool(args.tissue), tissue_bright=args.tissue_bright,
+                             tissue_spread=args.tissue_spread, tissue_min_pixels=args.tissue_min_pixels)
         stem = os.path.join(args.save_dir, os.path.splitext(os.path.basename(path))[0])
         mask = pred.mask.cpu().numpy()
         Image.fromarray(mask).save(stem + "_mask.png")
@@ -770,6 +975,8 @@ def predict_files(args) -> dict:
             Image.fromarray((votes * 255 // pred.members).astype(np.uint8)).save(stem + "_votes.png")
         if pred.regions is not None:
             write_regions_csv(stem + "_regions.csv", pred.regions)
+        if pred.tissue is not None:
+            Image.fromarray(pred.tissue.cpu().numpy()).save(stem + "_tissue.png")
         rec = image_record(path, pred)
         doc["images"].append(rec)
         c = rec["counts"]

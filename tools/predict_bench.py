@@ -27,6 +27,12 @@ move from the shapes, on the network's own mask and on adversarial masks (a serp
 over every seam; noise at p = 0.59 and specks: very many); (P) `predict_image` with and without
 `regions=True, min_region, fill_holes`, alternating, host clock; (H) the same tail done on the host with
 scipy.ndimage and numpy on the planes of the same run, and whether both give the same mask and table.
+With `--tissue` the tool times the tissue mask instead (`... --tissue > profiles/predict_tissue.txt`):
+`predict_image(..., tissue=True)`'s loop restated around HIP events (tissue plane, window counts, the one read of the
+counts, gather, forward and stitch of the kept tiles, the stitch of constants for the skipped ones, the class counts
+over the tissue), alternating with the same loop without the rule, (a) on the mosaic as it is (the overhead where
+nothing is skipped) and (b) with its right half replaced by the reference's glass model (the speed-up beside the
+share of tiles forwarded).
 One warm-up pass, then `rounds` passes of (A) and (B) alternating; the median pass is reported with the
 min-max spread. Before timing, (A)'s mask is checked against the thresholds applied to its own planes, and
 (B)'s host mask against it away from the seams. Nothing here is a threshold: the tool records times.
@@ -319,6 +325,144 @@ def tta_report(a, net, image, plan, t_out, t_sel, dev, mpix):
     return 0 if ok else 1
 
 
+# ----------------------------------------------------------------------------- --tissue
+TISSUE_STAGES = ("upload", "tissue plane", "window counts", "read of the counts", "gather", "forward", "stitch",
+                 "stitch of constants", "class counts", "final copy", "whole pass")
+
+
+def tissue_pass(net, image, plan, batch, t_out, t_sel, dev, rule):
+    """One pass of predict_image's loop, with the tissue rule (bright, spread, min_pixels) or without (None), with an
+    event after every stage: ({stage: ms}, mask, kept | None, counts [8 | 4])."""
+    ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
+    tile, halo, H, W = plan.tile, plan.halo, plan.H, plan.W
+    marks, consts = [], []
+    with torch.no_grad():
+        t = [ev() for _ in range(8)]
+        t[0].record()
+        img = torch.from_numpy(image).to(dev)
+        origins = torch.from_numpy(plan.origins).to(dev)
+        t[1].record()
+        keep = glass = None
+        if rule:
+            glass = PR.tissue_plane(img, rule[0], rule[1])
+        t[2].record()
+        if rule:
+            window = PR.tile_tissue_counts(glass, origins, tile, tile)
+        t[3].record()
+        if rule:
+            keep = window.cpu().numpy() >= rule[2]
+        t[4].record()
+        logit = torch.empty(plan.Hc, plan.Wc, device=dev)
+        selp = torch.empty_like(logit)
+        mask = torch.empty(plan.Hc, plan.Wc, dtype=torch.uint8, device=dev)
+        prob = torch.empty_like(mask)
+        counts = torch.zeros(8 if rule else 4, dtype=torch.int64, device=dev)
+        run_host, run = PR._kept_origins(plan.origins, origins, keep)
+        x_buf = torch.empty(min(batch, plan.n), 3, tile, tile, device=dev)
+        for a in range(0, len(run_host), batch):
+            b = min(a + batch, len(run_host))
+            e = [ev() for _ in range(4)]
+            e[0].record()
+            x = PR.tile_gather(img, run[a:b], tile, tile, "RGB", out=x_buf[:b - a])
+            e[1].record()
+            out, sel, _ = net(x)
+            e[2].record()
+            PR.tile_stitch(out, sel, run_host[a:b], run[a:b], halo, H, W, t_out, t_sel, logit, selp, mask, prob, counts[:4])
+            e[3].record()
+            marks.append(e)
+        if rule:
+            for out, sel, oh, od in PR._Skipped(min(batch, plan.n), tile, True, dev).batches(plan.origins, keep):
+                e = [ev(), ev()]
+                e[0].record()
+                PR.tile_stitch(out, sel, oh, od, halo, H, W, t_out, t_sel, logit, selp, mask, prob, counts[:4])
+                e[1].record()
+                consts.append(e)
+        t[5].record()
+        if rule:
+            PR.tissue_class_counts(mask[:H, :W], glass, counts[4:])
+        t[6].record()
+        m, p = mask[:H, :W].cpu(), prob[:H, :W].cpu()
+        c = counts.cpu()
+        t[7].record()
+        torch.cuda.synchronize()
+    ms = {"upload": t[0].elapsed_time(t[1]), "tissue plane": t[1].elapsed_time(t[2]), "window counts": t[2].elapsed_time(t[3]),
+          "read of the counts": t[3].elapsed_time(t[4]), "gather": sum(e[0].elapsed_time(e[1]) for e in marks),
+          "forward": sum(e[1].elapsed_time(e[2]) for e in marks), "stitch": sum(e[2].elapsed_time(e[3]) for e in marks),
+          "stitch of constants": sum(e[0].elapsed_time(e[1]) for e in consts), "class counts": t[5].elapsed_time(t[6]),
+          "final copy": t[6].elapsed_time(t[7]), "whole pass": t[0].elapsed_time(t[7])}
+    return ms, m.numpy(), keep, c.numpy()
+
+
+def tissue_report(a, net, image, plan, t_out, t_sel, dev, mpix):
+    """--tissue: the passes with and without the rule alternating, on the mosaic and on its half-glass version."""
+    rule = (PR.TISSUE_BRIGHT, PR.TISSUE_SPREAD, 1)
+    half = image.copy()
+    rng = np.random.default_rng(1)
+    half[:, a.size // 2:] = np.floor(255 * np.clip(0.96 + 0.005 * rng.standard_normal(half[:, a.size // 2:].shape), 0, 1) + 0.5)
+    kw = dict(tile=a.tile, halo=a.halo, batch_size=a.batch)
+
+    def row(rows, k):
+        v = [t[k] for t in rows]
+        return statistics.median(v), f"{statistics.median(v):10.3f} [{min(v):.3f} .. {max(v):.3f}]"
+
+    ok = True
+    for name, im in (("(a) the mosaic as it is", image), ("(b) the right half replaced by the glass model", half)):
+        # ---- warm-up and checks: the restated loop against predict_image
+        _, mask, keep, counts = tissue_pass(net, im, plan, a.batch, t_out, t_sel, dev, rule)
+        tissue_pass(net, im, plan, a.batch, t_out, t_sel, dev, None)
+        pred = PR.predict_image(net, im, tissue=True, **kw)
+        same = bool(np.array_equal(pred.mask.cpu().numpy(), mask)) and bool(np.array_equal(pred.tiles_kept[0], keep)) and \
+            counts[:4].tolist() == pred.counts.tolist() and counts[4:].tolist() == pred.tissue_counts.tolist()
+        ok = ok and same
+        off = PR.predict_image(net, im, **kw)
+        cover = torch.from_numpy(np.kron(keep.reshape(plan.grid), np.ones((plan.core, plan.core), bool))[:plan.H, :plan.W]).to(dev)
+        kept_equal = bool(torch.equal(pred.logit[cover], off.logit[cover])) and bool(torch.equal(pred.mask[cover], off.mask[cover]))
+        ok = ok and kept_equal
+        kept_n = int(keep.sum())
+        print(f"{name}: tissue pixels {int(pred.tissue_counts[3])} of {plan.H * plan.W} "
+              f"({int(pred.tissue_counts[3]) / (plan.H * plan.W):.4f}); tiles forwarded {kept_n} of {plan.n} "
+              f"({kept_n / plan.n:.4f}) in {-(-kept_n // a.batch)} batches (the last of {kept_n % a.batch or a.batch}); "
+              f"{plan.n - kept_n} skipped")
+        print(f"    restated loop == predict_image(tissue=True): {same}; kept pixels bit-equal to tissue=False: {kept_equal}")
+        print(f"    counts {dict(zip(PR.COUNT_NAMES, pred.counts.tolist()))}; over tissue "
+              f"{dict(zip(PR.COUNT_NAMES, pred.tissue_counts.tolist()))}; tumor fraction of selected {pred.tumor_fraction:.4f}, "
+              f"of tissue {pred.tumor_fraction_of_tissue:.4f}")
+        # ---- timing: without and with the rule, alternating in one process
+        t_off, t_on, h_off, h_on = [], [], [], []
+        for _ in range(a.rounds):
+            t_off.append(tissue_pass(net, im, plan, a.batch, t_out, t_sel, dev, None)[0])
+            t_on.append(tissue_pass(net, im, plan, a.batch, t_out, t_sel, dev, rule)[0])
+            for extra, into in ((dict(), h_off), (dict(tissue=True), h_on)):
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                p = PR.predict_image(net, im, **kw, **extra)
+                p.mask.cpu(), p.prob8.cpu()
+                torch.cuda.synchronize()
+                into.append((time.perf_counter() - t) * 1e3)
+        print(f"    {'stage (HIP events)':<24}{'tissue=False':>34}{'tissue=True':>34}")
+        med = {}
+        for k in TISSUE_STAGES:
+            (m0, s0), (m1, s1) = row(t_off, k), row(t_on, k)
+            med[k] = (m0, m1)
+            print(f"    {k:<24}{s0:>34}{s1:>34}")
+        new = sum(med[k][1] for k in ("tissue plane", "window counts", "class counts"))
+        gs = med["gather"][1] + med["stitch"][1] + med["stitch of constants"][1]
+        px = plan.H * plan.W
+        moved = px * 3 + px + 1.6 * px + 2 * px  # plane: 3 B in, 1 B out; window counts: about 1.6 x the plane; class counts: mask + plane
+        print(f"    new launches (plane + window counts + class counts): {new:.3f} ms ({moved / 1e6:.1f} MB from the shapes, "
+              f"{moved / new / 1e6:.1f} GB/s); gather + stitch (+ constants) of the same pass: {gs:.3f} ms; the one extra read: "
+              f"{med['read of the counts'][1]:.3f} ms")
+        ratio = med["whole pass"][1] / med["whole pass"][0]
+        print(f"    whole pass tissue=True / tissue=False: {ratio:.4f} (forwarded / total tiles {kept_n / plan.n:.4f}); forward "
+              f"{med['forward'][1] / med['forward'][0]:.4f}; {mpix / med['whole pass'][1] * 1e3:.1f} against "
+              f"{mpix / med['whole pass'][0] * 1e3:.1f} Mpixel/s")
+        m0, m1 = statistics.median(h_off), statistics.median(h_on)
+        print(f"    predict_image + mask and prob8 to the host (host clock): {m0:.2f} [{min(h_off):.2f} .. {max(h_off):.2f}] without, "
+              f"{m1:.2f} [{min(h_on):.2f} .. {max(h_on):.2f}] with the rule: ratio {m1 / m0:.4f}")
+    print("checks passed:", ok)
+    return 0 if ok else 1
+
+
 # ----------------------------------------------------------------------------- --regions (DESIGN.md §7h)
 REGION_STAGES = ("local", "seam", "flatten", "roots to rows (torch)", "stats", "action (torch)", "apply")
 
@@ -525,6 +669,7 @@ def main():
     ap.add_argument("--fp32_path", default="exact", choices=["exact", "split"])
     ap.add_argument("--tta", action="store_true", help="time test-time augmentation: none, flips, d4 and d4 on the host")
     ap.add_argument("--regions", action="store_true", help="time region labelling, the table and the clean-up")
+    ap.add_argument("--tissue", action="store_true", help="time the tissue mask: overhead where nothing is skipped, speed-up on a half-glass image")
     ap.add_argument("--min_region", type=int, default=64)
     ap.add_argument("--fill_holes", type=int, default=64)
     a = ap.parse_args()
@@ -553,6 +698,8 @@ def main():
     print(f"(A) {plan!r}: {plan.n} tiles in {-(-plan.n // a.batch)} batches")
     if a.tta:
         return tta_report(a, net, image, plan, t_out, t_sel, dev, mpix)
+    if a.tissue:
+        return tissue_report(a, net, image, plan, t_out, t_sel, dev, mpix)
     if a.regions:
         return regions_report(a, net, image, plan, t_out, t_sel, dev, mpix)
     n_old = (a.size // a.tile) ** 2
