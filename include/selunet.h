@@ -730,6 +730,52 @@ int selunet_patch_auc(const float* out, const float* sel, const float* target,
                       int32_t n, int64_t hw, float t_sel,
                       unsigned long long* rows, void* stream);
 
+/* ---- boundary-distance metrics -------------------------------------------------
+ * Where a selective network abstains and how far its errors lie from the annotation: an exact
+ * Euclidean distance transform of a thresholded plane, and the counts of selunet_seg_metrics by
+ * distance band and per image. Integer arithmetic and integer atomics only: every result is the same
+ * bit for bit on every run. */
+/* The value of selunet_edt_sq for every pixel of an image that holds one class only. */
+#define SELUNET_EDT_NONE INT32_MAX
+#define SELUNET_EDT_MAX_SIDE 4096
+/* Squared Euclidean distance to the other class. x: fp32 [n][h][w]; a pixel is foreground iff
+ * x >= t (a NaN is background). d2: int32 [n][h][w] = the smallest (y - y')^2 + (x - x')^2 over the
+ * pixels (y', x') of the same image whose class differs from the pixel's own, hence >= 1;
+ * SELUNET_EDT_NONE throughout an image of one class. Exact for 1 <= h, w <= SELUNET_EDT_MAX_SIDE
+ * (2 * 4095^2 < 2^31). Two launches (columns, then rows in place in d2), no workspace.
+ * EINVAL: a null pointer; n < 1; h or w outside [1, SELUNET_EDT_MAX_SIDE]; n * max(h, w) >= 2^31;
+ * x or d2 not 4-B aligned. */
+int selunet_edt_sq(const float* x, float t, int32_t n, int32_t h, int32_t w, int32_t* d2, void* stream);
+/* The six words of selunet_seg_metrics by distance band. out / sel / target: fp32 [n][hw] (sel
+ * nullable) with selunet_seg_metrics' rules for thresholds, NaNs, labels and a null sel; d2_target:
+ * int32 [n][hw], selunet_edt_sq of the target. r2: HOST array of k squared radii, strictly increasing,
+ * r2[0] >= 1, 1 <= k <= SELUNET_BAND_MAX (read during the call only). bins: uint64 [k + 2][6],
+ * caller-zeroed, accumulated across calls; row b += the six counts over the pixels of band b:
+ *   band 0: d2 <= r2[0]; band j (0 < j < k): r2[j-1] < d2 <= r2[j]; band k: r2[k-1] < d2, finite;
+ *   band k + 1: d2 == SELUNET_EDT_NONE (images without a contour).
+ * The sum of the rows is what selunet_seg_metrics counts over the same pixels.
+ * EINVAL: a null pointer (sel may be null); n < 1, hw < 1 or n * hw > 2^40; a bad k or r2; out, sel,
+ * target or d2_target not 16-B aligned; bins not 8-B aligned. */
+#define SELUNET_BAND_MAX 15
+int selunet_boundary_bands(const float* out, const float* sel, const float* target, const int32_t* d2_target,
+                           int32_t n, int64_t hw, float t_out, float t_sel, const int32_t* r2, int32_t k,
+                           unsigned long long* bins, void* stream);
+/* Per-image error distances. d2_pred: selunet_edt_sq of out at t_out (always of the full prediction
+ * mask, whatever sel). With label = (int)(uint8_t)target and pred = out >= t_out as selunet_seg_metrics,
+ * over the pixels that are selected (sel == NULL or sel >= t_sel): a false positive has label 0 and
+ * pred 1, a false negative label 1 and pred 0. rows: uint64 [n][6], caller-zeroed; row i becomes
+ *   word 0 = max(word 0, max of d2_target over the false positives)   (0 when there are none),
+ *   word 1 = max(word 1, max of d2_pred over the false negatives),
+ *   words 2, 3 += false positives with d2_target <= tol_sq, false negatives with d2_pred <= tol_sq,
+ *   words 4, 5 += false positives, false negatives.
+ * Word 0 is the squared directed Hausdorff distance from the predicted region to the label region
+ * (SELUNET_EDT_NONE: the label region is empty), word 1 the converse.
+ * EINVAL: a null pointer (sel may be null); n < 1; hw outside [1, 2^24]; tol_sq < 0; a pointer not
+ * 4-B aligned, or not 16-B aligned when hw % 4 == 0 (the vector path); rows not 8-B aligned. */
+int selunet_boundary_rows(const float* out, const float* sel, const float* target, const int32_t* d2_target,
+                          const int32_t* d2_pred, int32_t n, int64_t hw, float t_out, float t_sel,
+                          int32_t tol_sq, unsigned long long* rows, void* stream);
+
 /* ---- whole-image prediction I/O --------------------------------------------
  * A trained network applied to an image of any size: overlapping tiles are gathered from the image, run
  * through the eval-mode forward, and the tiles' cores (tile minus a halo on every side) stitched into

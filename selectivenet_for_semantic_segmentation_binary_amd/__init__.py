@@ -12,6 +12,8 @@ Drop-in replacements for the reference's hot path (yellofi/SelectiveNet_for_sema
 * `SelectiveSweep`                       risk-coverage sweep of eval.py's --s_cut_off in one pass
 * `PatchReport`                          per-patch counts, get_performance metrics and exact ROC AUC
                                         <- utils/compute_metric.py:93-148 (unused there)
+* `BoundaryReport`,                      errors and rejections by distance to the label contour, Hausdorff distance
+  `boundary_distance_sq`                 per patch; the exact Euclidean distance transform on the device
 * `predict_image`, `TilePlan`             whole-image prediction: tiles gathered and stitched on the device,
                                         optionally averaged over the image's flips / D4 orientations (tta=)
 * `label_regions`, `region_table`,       connected regions of a prediction mask, their exact table and the
@@ -23,7 +25,7 @@ Drop-in replacements for the reference's hot path (yellofi/SelectiveNet_for_sema
 All compute runs in libselunet.so (HIP, gfx950); there is no CPU fallback.
 """
 from .layout import count_params, state_dict_keys  # noqa: F401
-from .metrics import PatchReport, SelectiveSweep  # noqa: F401
+from .metrics import BoundaryReport, PatchReport, SelectiveSweep, boundary_distance_sq  # noqa: F401
 from .model import CBR_2D, UNet, UNet_B  # noqa: F401
 from .optim import Adam  # noqa: F401
 from .predict import TilePlan, clean_mask, label_regions, predict_image, region_table, tissue_plane  # noqa: F401

@@ -24,6 +24,10 @@ GEMM_BM = 128
 ADAM_CHUNK = 4096
 SWEEP_MAX = 256  # SELUNET_SWEEP_MAX
 AUC_CHUNK = 4096  # SELUNET_AUC_CHUNK
+EDT_NONE = 2 ** 31 - 1  # SELUNET_EDT_NONE
+EDT_MAX_SIDE = 4096  # SELUNET_EDT_MAX_SIDE
+BAND_MAX = 15  # SELUNET_BAND_MAX
+EDT_ROW_CHUNK = 256  # pixels of a row one sweep of the EDT row pass's workgroup takes (csrc/boundary.hip)
 
 
 class Source(ctypes.Structure):
@@ -199,6 +203,10 @@ SIGNATURES = {
     "selunet_seg_metrics_sweep": (c_int32, [P, P, P, c_int64, c_float, P, c_int32, P, P]),
     "selunet_seg_metrics_rows": (c_int32, [P, P, P, c_int32, c_int64, c_float, c_float, P, P]),
     "selunet_patch_auc": (c_int32, [P, P, P, c_int32, c_int64, c_float, P, P]),
+    "selunet_edt_sq": (c_int32, [P, c_float, c_int32, c_int32, c_int32, P, P]),
+    "selunet_boundary_bands": (c_int32, [P, P, P, P, c_int32, c_int64, c_float, c_float, ctypes.POINTER(c_int32),
+                                         c_int32, P, P]),
+    "selunet_boundary_rows": (c_int32, [P, P, P, P, P, c_int32, c_int64, c_float, c_float, c_int32, P, P]),
     "selunet_tile_gather": (c_int32, [P, c_int32, c_int32, P, c_int32, c_int32, c_int32, c_int32, P, P]),
     "selunet_tile_stitch": (c_int32, [P, P, P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                       c_float, c_float, P, P, P, P, P, P]),

@@ -22,6 +22,12 @@ Per-patch report (MI355X path only): --patch_report 1 writes one row per test pa
 (`metrics.PatchReport`: confusion matrix, the reference's unused `get_performance` metrics of
 utils/compute_metric.py:93-148 with an exact ROC AUC of the logit; with --select_eval also over the
 selected pixels) to patch_performance.csv and a summary to patch_performance.json.
+Boundary report (MI355X path only): --boundary_report 1 adds the distance view from the same pass
+(`metrics.BoundaryReport`): an exact on-device Euclidean distance transform of the label and
+prediction masks, the Evaluator's counts, coverage and risk by band of distance to the label contour
+(--boundary_bands R [R ...], default 1 2 4 8 16) in boundary_bands.json / .csv, and per patch the Hausdorff
+distance and the scores that forgive errors within --boundary_tolerance T (default 2) pixels of the other mask
+in patch_boundary.csv, with a summary in patch_boundary.json. Over the selected pixels with --select_eval.
 fp32 conv path (MI355X path only): --fp32_path split runs the fp32 forward on the training forward's
 split-fp16 kernels (`UNet_B(fp32_eval_path="split")`); the default, exact, keeps the exact
 fp32 kernels. Not with --compute_dtype bf16.
@@ -74,7 +80,27 @@ def parse_arguments(argv=None):
                         help='write one row per test patch (patch_performance.csv / .json)')
     parser.add_argument('--fp32_path', type=str, default='exact', choices=['exact', 'split'],
                         help='conv kernels of the fp32 forward: exact fp32, or the split-fp16 kernels of training')
+    parser.add_argument('--boundary_report', type=bool, default=False,
+                        help='errors and rejections by distance to the label contour, Hausdorff distance per patch '
+                             '(boundary_bands.json / .csv, patch_boundary.csv / .json)')
+    parser.add_argument('--boundary_bands', type=float, nargs='+', default=[1, 2, 4, 8, 16],
+                        help='outer radii (pixels) of the distance bands, strictly increasing from >= 1')
+    parser.add_argument('--boundary_tolerance', type=float, default=2,
+                        help='errors within this distance (pixels) of the other mask count as correct in the '
+                             'tolerant scores')
     args = parser.parse_args(argv)
+    if args.boundary_report:
+        from . import metrics as MT
+        try:
+            MT.band_edges_sq(args.boundary_bands)
+        except ValueError as e:
+            parser.error(f'--boundary_bands: {e}')
+        if not 0 <= args.boundary_tolerance < 4096 * 2 ** 0.5:
+            parser.error('--boundary_tolerance: a distance in pixels, >= 0 and below the diagonal of 4096 x 4096')
+    else:
+        # off: the namespace, and with it the printed args= line, is what it is without the three flags
+        for name in ('boundary_report', 'boundary_bands', 'boundary_tolerance'):
+            delattr(args, name)
     if args.fp32_path == 'split' and args.compute_dtype == 'bf16':
         parser.error('--fp32_path split is an fp32 path: not with --compute_dtype bf16')
     if args.s_cut_off_steps is not None and not 1 <= args.s_cut_off_steps <= 255:
@@ -144,6 +170,11 @@ def evaluate(args):
     if getattr(args, "patch_report", False):
         report = MT.PatchReport(device, selective=bool(args.select_eval), rule="eval", cut_off=args.cut_off,
                                 s_cut_off=args.s_cut_off, output_scale=args.single_scale)
+    boundary = None
+    if getattr(args, "boundary_report", False):
+        boundary = MT.BoundaryReport(device, selective=bool(args.select_eval), radii=args.boundary_bands,
+                                     tolerance=args.boundary_tolerance, rule="eval", cut_off=args.cut_off,
+                                     s_cut_off=args.s_cut_off, output_scale=args.single_scale)
     seen = 0  # patches fed so far: the loader walks the set in order
     print("Model Prediction...")
     with torch.no_grad():
@@ -173,11 +204,13 @@ def evaluate(args):
             ev.add_batch(output, target, selection)
             if sweep is not None:
                 sweep.add_batch(output, target, selection)
+            n = output.shape[0]
+            ids = None if ds.ids is None else list(ds.ids[seen:seen + n])
+            seen += n
             if report is not None:
-                n = output.shape[0]
-                report.add_batch(output, target, selection,
-                                 ids=None if ds.ids is None else list(ds.ids[seen:seen + n]))
-                seen += n
+                report.add_batch(output, target, selection, ids=ids)
+            if boundary is not None:
+                boundary.add_batch(output, target, selection, ids=ids)
     cm = ev.confusion_matrix()
     selected, total = ev.selected_total()
     prec, rec = MT.precision(cm), MT.recall(cm)
@@ -204,7 +237,49 @@ def evaluate(args):
         res = dict(res, risk_coverage=report_sweep(sweep.curve(), args.target_coverage, args.save_dir))
     if report is not None:
         res = dict(res, patch_report=report_patches(report.rows(), args.save_dir))
+    if boundary is not None:
+        res = dict(res, boundary_report=report_boundary(boundary.bands(), boundary.rows(), boundary.radii,
+                                                        boundary.tolerance, args.save_dir))
     return res
+
+
+def _cell(v):
+    """A CSV cell: integers as integers, floats by repr."""
+    return repr(v) if isinstance(v, float) else str(v)
+
+
+def report_boundary(bands, rows, radii, tolerance, save_dir):
+    """Print the band table and the Hausdorff summary and write boundary_bands.json / .csv (one row per
+    distance band), patch_boundary.csv (one row per patch) and patch_boundary.json (the summary)."""
+    from . import metrics as MT
+
+    doc = MT.boundary_report_summary(rows)
+    doc["tolerance"] = tolerance
+    print('    boundary report: pixels, coverage and risk by distance d to the label contour')
+    print('    ' + ' '.join(f'{c:>14}' for c in ("band", "pixel_share", "coverage", "risk", "rejected_share",
+                                                  "error_share")))
+    for r in bands:
+        name = ("no contour" if r["r_lo"] != r["r_lo"] else
+                f'd > {r["r_lo"]:g}' if r["r_hi"] == float("inf") else f'{r["r_lo"]:g} < d <= {r["r_hi"]:g}')
+        print('    ' + f'{name:>14} ' + ' '.join(f'{r[c]:14.6f}' for c in ("pixel_share", "coverage", "risk",
+                                                                               "rejected_share", "error_share")))
+    print(f'    Hausdorff distance over {doc["patches"]} patches: mean {doc["mean_hausdorff"]:.6f} median '
+          f'{doc["median_hausdorff"]:.6f} ({doc["infinite_hausdorff"]} infinite, {doc["zero_hausdorff"]} zero)')
+    os.makedirs(save_dir, exist_ok=True)
+    with open(os.path.join(save_dir, "boundary_bands.json"), "w") as fh:
+        json.dump({"radii": list(radii), "bands": bands}, fh, indent=1)
+    with open(os.path.join(save_dir, "boundary_bands.csv"), "w") as fh:
+        fh.write(",".join(MT.BAND_COLUMNS) + "\n")
+        for r in bands:
+            fh.write(",".join(_cell(r[c]) for c in MT.BAND_COLUMNS) + "\n")
+    cols = MT.boundary_report_columns(rows)
+    with open(os.path.join(save_dir, "patch_boundary.csv"), "w") as fh:
+        fh.write(",".join(cols) + "\n")
+        for r in rows:
+            fh.write(",".join(_cell(r[c]) for c in cols) + "\n")
+    with open(os.path.join(save_dir, "patch_boundary.json"), "w") as fh:
+        json.dump(doc, fh, indent=1)
+    return dict(doc, bands=bands, rows=rows)
 
 
 def report_patches(rows, save_dir):

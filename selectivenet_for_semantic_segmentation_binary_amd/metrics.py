@@ -21,6 +21,11 @@ cut-off to a wanted coverage.
 `selunet_patch_auc`): the counts per image and the exact integer Mann-Whitney statistic of the
 prediction logit, from which `patch_performance` forms the reference's unused `get_performance`
 (utils/compute_metric.py:93-148) — accuracy, recall, precision, f1 score and ROC AUC per patch.
+
+`BoundaryReport` adds the distance view: an exact on-device Euclidean distance transform
+of the label and prediction masks (`selunet_edt_sq`), the `SegMetrics` counts by band of distance to the
+label contour (`band_table`: where the network errs and abstains) and per patch the directed Hausdorff
+distances and boundary-tolerant scores (`boundary_patch`).
 """
 from __future__ import annotations
 
@@ -366,4 +371,226 @@ def patch_report_summary(rows) -> dict:
         doc[prefix + "nan_auc"] = int(len(auc) - len(finite))
         doc[prefix + "mean_auc"] = float(finite.mean()) if len(finite) else float("nan")
         doc[prefix + "median_auc"] = float(np.median(finite)) if len(finite) else float("nan")
+    return doc
+
+
+# ----------------------------------------------------------------------------- boundary distances
+BAND_COUNTS = ("cm00", "cm01", "cm10", "cm11", "selected", "pixels")
+BAND_COLUMNS = ("band", "r_lo", "r_hi") + BAND_COUNTS + (
+    "pixel_share", "coverage", "errors", "risk", "rejected", "rejected_share", "error_share",
+    "cum_pixel_share", "cum_rejected_share", "cum_error_share")
+BOUNDARY_WORDS = ("fp_max_d2", "fn_max_d2", "fp_within", "fn_within", "fp", "fn")
+BOUNDARY_METRICS = ("hausdorff", "hd_pred_to_label", "hd_label_to_pred", "tolerant_accuracy", "tolerant_tumor_iou")
+
+
+def band_edges_sq(radii) -> np.ndarray:
+    """floor(r^2) of the band radii, in float64: a pixel lies within r of the contour exactly when its
+    integer squared distance is <= floor(r^2). The radii and their floored squares must be strictly
+    increasing from >= 1 (two radii between the same two integers' roots would make an empty band), at
+    most `BAND_MAX` of them, below the largest distance of a 4096 x 4096 plane."""
+    r = np.asarray(radii, np.float64).reshape(-1)
+    if r.size < 1 or r.size > K.BAND_MAX:
+        raise ValueError(f"boundary bands: {r.size} radii, between 1 and {K.BAND_MAX} are allowed")
+    if not np.all(np.isfinite(r)) or np.any(r < 1) or np.any(np.diff(r) <= 0):
+        raise ValueError(f"boundary bands: the radii must be finite, >= 1 and strictly increasing, got {r.tolist()}")
+    r2 = np.floor(r * r)
+    if np.any(np.diff(r2) <= 0) or r2[-1] >= K.EDT_NONE:
+        raise ValueError(f"boundary bands: the floored squares {r2.tolist()} of the radii must be strictly "
+                         f"increasing and below 2^31 - 1")
+    return r2
+
+
+def boundary_distance_sq(x: torch.Tensor, t: float, out: torch.Tensor | None = None) -> torch.Tensor:
+    """`selunet_edt_sq` of an (N, H, W) contiguous cuda fp32 tensor: int32 (N, H, W), the squared Euclidean
+    distance of every pixel to the nearest pixel of the other class of its image (foreground: x >= t),
+    `K.EDT_NONE` throughout an image of one class. `out` (same shape, int32, contiguous) is overwritten."""
+    if x.device.type != "cuda" or x.dtype != torch.float32 or not x.is_contiguous():
+        raise RuntimeError("boundary_distance_sq: x must be a contiguous cuda fp32 tensor")
+    if x.dim() != 3:
+        raise ValueError(f"boundary_distance_sq: x must be (N, H, W), got {tuple(x.shape)}")
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.int32, device=x.device)
+    elif out.device != x.device or out.dtype != torch.int32 or not out.is_contiguous():
+        raise RuntimeError("boundary_distance_sq: out must be a contiguous int32 tensor on x's device")
+    elif out.shape != x.shape:
+        raise ValueError(f"boundary_distance_sq: out of shape {tuple(out.shape)} for x of {tuple(x.shape)}")
+    n, h, w = x.shape
+    K.call("selunet_edt_sq", K.ptr(x), float(t), n, h, w, K.ptr(out), K.stream_ptr())
+    return out
+
+
+def _ratio(a, b):
+    return a / b if b else float("nan")
+
+
+def band_table(bins, radii) -> list:
+    """One row per band from the [(k+2), 6] counts of `BoundaryReport.raw_bands()`: bands 0..k by distance
+    to the label contour (r_lo < d <= r_hi, r_hi = inf for band k), then band k+1, the patches without a
+    contour (r_lo = r_hi = NaN). errors = cm01 + cm10 (over the selected pixels), risk = errors / selected,
+    coverage = selected / pixels, rejected = pixels - selected; the shares are of the totals over all bands
+    (NaN where the total is 0) and the cum_ columns their running sums in band order."""
+    bins = np.asarray(bins, np.int64)
+    radii = [float(r) for r in radii]
+    k = len(radii)
+    if bins.shape != (k + 2, 6):
+        raise ValueError(f"band_table: bins of shape {bins.shape} for {k} radii")
+    pixels, selected = bins[:, 5], bins[:, 4]
+    errors, rejected = bins[:, 1] + bins[:, 2], pixels - selected
+    tot_p, tot_r, tot_e = int(pixels.sum()), int(rejected.sum()), int(errors.sum())
+    lo = [0.0] + radii + [float("nan")]
+    hi = radii + [float("inf"), float("nan")]
+    rows, cum = [], [0, 0, 0]
+    for b in range(k + 2):
+        cum = [cum[0] + int(pixels[b]), cum[1] + int(rejected[b]), cum[2] + int(errors[b])]
+        row = {"band": b, "r_lo": lo[b], "r_hi": hi[b]}
+        row.update({name: int(bins[b, i]) for i, name in enumerate(BAND_COUNTS)})
+        row.update({"pixel_share": _ratio(int(pixels[b]), tot_p), "coverage": _ratio(int(selected[b]), int(pixels[b])),
+                    "errors": int(errors[b]), "risk": _ratio(int(errors[b]), int(selected[b])),
+                    "rejected": int(rejected[b]), "rejected_share": _ratio(int(rejected[b]), tot_r),
+                    "error_share": _ratio(int(errors[b]), tot_e), "cum_pixel_share": _ratio(cum[0], tot_p),
+                    "cum_rejected_share": _ratio(cum[1], tot_r), "cum_error_share": _ratio(cum[2], tot_e)})
+        rows.append(row)
+    return rows
+
+
+def _root(d2) -> float:
+    d2 = int(d2)
+    return float("inf") if d2 >= K.EDT_NONE else float(np.sqrt(np.float64(d2)))
+
+
+def boundary_patch(words, counts, prefix="") -> dict:
+    """The boundary fields of one patch from its six `selunet_boundary_rows` words and its six
+    `selunet_seg_metrics_rows` counts. hd_pred_to_label = sqrt(word 0), the directed Hausdorff distance from
+    the predicted region to the label region (0 without a false positive, inf when there is one and the
+    label mask is empty); hd_label_to_pred = sqrt(word 1) the converse; hausdorff their maximum. The tolerant
+    scores count an error within the tolerance of the other mask as a hit of the tumor class:
+    tolerant_accuracy = (TP + TN + near) / counted, tolerant_tumor_iou = (TP + near) / (TP + FP + FN), NaN
+    where the denominator is 0."""
+    w = [int(v) for v in words]
+    tn, fp, fn, tp = (int(v) for v in counts[:4])
+    if (fp, fn) != (w[4], w[5]):
+        raise ValueError(f"boundary_patch: {w[4]} / {w[5]} false positives / negatives against a confusion "
+                         f"matrix with {fp} / {fn}")
+    near = w[2] + w[3]
+    row = dict(zip(BOUNDARY_WORDS, w))
+    a, b = _root(w[0]), _root(w[1])
+    row.update({"hausdorff": max(a, b), "hd_pred_to_label": a, "hd_label_to_pred": b,
+                "tolerant_accuracy": _ratio(tp + tn + near, tn + fp + fn + tp),
+                "tolerant_tumor_iou": _ratio(tp + near, tp + fp + fn)})
+    return {prefix + k: v for k, v in row.items()}
+
+
+class BoundaryReport:
+    """Where the network errs and abstains, by distance to the annotation's contour, in the pass eval
+    already makes. Per batch: the exact distance transform (`selunet_edt_sq`) of the target at 0.5 and of
+    the output at its logit threshold into two int32 planes kept between batches, `selunet_boundary_bands`
+    (the six `SegMetrics` counts per distance band, over the selected pixels when `selective`), and per patch
+    `selunet_boundary_rows` + `selunet_seg_metrics_rows` over all pixels and, when `selective`, again over
+    the selected ones. Nothing synchronises per batch: `bands()` / `rows()` copy once."""
+
+    def __init__(self, device, selective: bool, radii=(1, 2, 4, 8, 16), tolerance: float = 2.0,
+                 rule: str = "eval", cut_off: float = 0.5, s_cut_off: float = 0.5, output_scale: str = "sigmoid"):
+        self.device = device
+        self.selective = bool(selective)
+        self.radii = [float(r) for r in radii]
+        self.r2 = band_edges_sq(self.radii).astype(np.int32)
+        self._r2c = (K.c_int32 * len(self.r2))(*[int(v) for v in self.r2])
+        self.tolerance = float(tolerance)
+        if not np.isfinite(self.tolerance) or self.tolerance < 0 or self.tolerance ** 2 >= K.EDT_NONE:
+            raise ValueError(f"BoundaryReport: tolerance must be finite, >= 0 and below 2^15.5, got {tolerance}")
+        self.tol_sq = int(np.floor(np.float64(self.tolerance) ** 2))
+        self.t_out = logit_threshold(rule, cut_off, output_scale)
+        self.t_sel = logit_threshold(rule, s_cut_off, output_scale)
+        self.bins = torch.zeros(len(self.r2) + 2, 6, dtype=torch.int64, device=device)  # uint64 bits
+        self._store = None  # int32, 2 planes [n][h][w]: the distances of the target and of the prediction
+        self.reset()
+
+    def reset(self):
+        self.bins.zero_()
+        self._batches = []  # (n, device int64 tensor [passes][n*6 + n*6] of uint64 bits)
+        self._ids = []
+
+    def add_batch(self, output: torch.Tensor, target: torch.Tensor, selection: torch.Tensor | None = None, ids=None):
+        for name, t in (("output", output), ("target", target), ("selection", selection)):
+            if t is not None and (t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise RuntimeError(f"BoundaryReport.add_batch: {name} must be a contiguous cuda fp32 tensor")
+        if output.dim() != 3:
+            raise ValueError(f"BoundaryReport.add_batch: output must be (N, H, W), got {tuple(output.shape)}")
+        if target.shape != output.shape or (selection is not None and selection.shape != output.shape):
+            raise ValueError("BoundaryReport.add_batch: output, target and selection must have the same shape")
+        if self.selective and selection is None:
+            raise ValueError("selective BoundaryReport needs the selection logits")
+        n, hw = output.shape[0], output.shape[1] * output.shape[2]
+        if ids is not None and len(ids) != n:
+            raise ValueError(f"BoundaryReport.add_batch: {len(ids)} ids for {n} patches")
+        if hw % 4 or hw > 1 << 20 or max(output.shape[1:]) > K.EDT_MAX_SIDE:  # before anything is counted
+            raise ValueError(f"BoundaryReport.add_batch: patches of {tuple(output.shape[1:])}: H * W must be a "
+                             f"multiple of 4 and at most 2^20, H and W at most {K.EDT_MAX_SIDE}")
+        if self._store is None or self._store.numel() < 2 * output.numel() or self._store.device != output.device:
+            self._store = torch.empty(2 * output.numel(), dtype=torch.int32, device=output.device)
+        planes = self._store[:2 * output.numel()].view(2, *output.shape)
+        d2_target = boundary_distance_sq(target, 0.5, out=planes[0])
+        d2_pred = boundary_distance_sq(output, self.t_out, out=planes[1])
+        stream = K.stream_ptr()
+        sel = selection if self.selective else None
+        K.call("selunet_boundary_bands", K.ptr(output), K.ptr(sel), K.ptr(target), K.ptr(d2_target), n, hw,
+               self.t_out, self.t_sel, self._r2c, len(self.r2), K.ptr(self.bins), stream)
+        passes = [None, selection] if self.selective else [None]
+        buf = torch.zeros(len(passes), n * 12, dtype=torch.int64, device=output.device)
+        for k, s in enumerate(passes):
+            K.call("selunet_boundary_rows", K.ptr(output), K.ptr(s), K.ptr(target), K.ptr(d2_target), K.ptr(d2_pred),
+                   n, hw, self.t_out, self.t_sel, self.tol_sq, buf[k].data_ptr(), stream)
+            K.call("selunet_seg_metrics_rows", K.ptr(output), K.ptr(s), K.ptr(target), n, hw, self.t_out,
+                   self.t_sel, buf[k].data_ptr() + n * 6 * 8, stream)
+        self._batches.append((n, buf))
+        self._ids.extend([None] * n if ids is None else [str(i) for i in ids])
+
+    def raw_bands(self) -> np.ndarray:
+        c = self.bins.clone()
+        parallel.allreduce_sums(c)
+        return c.cpu().numpy().astype(np.int64)
+
+    def bands(self) -> list:
+        return band_table(self.raw_bands(), self.radii)
+
+    def rows(self) -> list:
+        if not self._batches:
+            return []
+        host = torch.cat([b.reshape(-1) for _, b in self._batches]).cpu().numpy()
+        passes = 2 if self.selective else 1
+        rows, at = [], 0
+        for n, _ in self._batches:
+            part = host[at:at + passes * n * 12].reshape(passes, 2, n, 6)
+            at += passes * n * 12
+            for i in range(n):
+                index = len(rows)
+                row = {"index": index, "id": self._ids[index] if self._ids[index] is not None else f"patch_{index}",
+                       "pixels": int(part[0, 1, i, 5])}
+                row.update(boundary_patch(part[0, 0, i], part[0, 1, i]))
+                if self.selective:
+                    row["selected"] = int(part[1, 1, i, 4])
+                    row.update(boundary_patch(part[1, 0, i], part[1, 1, i], prefix="sel_"))
+                rows.append(row)
+        return rows
+
+
+def boundary_report_columns(rows) -> tuple:
+    """Column order of patch_boundary.csv for these rows (with or without the selection fields)."""
+    cols = ("index", "id", "pixels") + BOUNDARY_WORDS + BOUNDARY_METRICS
+    if rows and "selected" in rows[0]:
+        cols += ("selected",) + tuple("sel_" + c for c in BOUNDARY_WORDS + BOUNDARY_METRICS)
+    return cols
+
+
+def boundary_report_summary(rows) -> dict:
+    """Number of patches, of patches with an infinite and with a zero Hausdorff distance, and the mean and
+    median of the finite ones (NaN when there is none); with selection the same over the selected pixels."""
+    doc = {"patches": len(rows)}
+    for prefix in ("", "sel_") if rows and "selected" in rows[0] else ("",):
+        hd = np.array([r[prefix + "hausdorff"] for r in rows], np.float64)
+        finite = hd[np.isfinite(hd)]
+        doc[prefix + "infinite_hausdorff"] = int(len(hd) - len(finite))
+        doc[prefix + "zero_hausdorff"] = int((hd == 0).sum())
+        doc[prefix + "mean_hausdorff"] = float(finite.mean()) if len(finite) else float("nan")
+        doc[prefix + "median_hausdorff"] = float(np.median(finite)) if len(finite) else float("nan")
     return doc
