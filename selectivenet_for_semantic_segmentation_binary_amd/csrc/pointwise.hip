@@ -1281,6 +1281,15 @@ __global__ void selective_finalize_kernel(const double* sums, double P, float la
   state[3] = (float)P;
 }
 
+// sigmoid(x) - t with q = sigmoid(-|x|): (1 - t) - q for x >= 0, q - t below. 1 / (1 + e^-x) - t rounds
+// sigmoid to 1 from x ~ 17 on, so a saturated logit on its target's side got gradient 0 where the value is
+// -e^-x (all of the gradient when every pixel is such a one); here that term is exact to fp32 rounding.
+__device__ __forceinline__ float sigmoid_minus_(float x, float t) {
+  const float e = __expf(-fabsf(x));
+  const float q = e * (1.0f / (1.0f + e));
+  return x >= 0.0f ? (1.0f - t) - q : q - t;
+}
+
 // HARD: selection and coverage are detached (selective_loss.py:75-76), so d_sel = 0 and the
 // output gradient carries the hard weight over the (constant) soft selection sum.
 template <bool HARD>
@@ -1295,13 +1304,13 @@ __global__ void selective_bwd_kernel(const float* __restrict__ out, const float*
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < P; i += (int64_t)gridDim.x * blockDim.x) {
     const float s = sigmoidf_(sel[i]);
     const float x = out[i], t = tgt[i];
-    const float px = sigmoidf_(x);
+    const float dx = sigmoid_minus_(x, t);
     if constexpr (HARD) {
-      d_out[i] = gl * (s > 0.5f ? 1.0f : 0.0f) * (px - t) * inv_s0;
+      d_out[i] = gl * (s > 0.5f ? 1.0f : 0.0f) * dx * inv_s0;
       d_sel[i] = 0.0f;
     } else {
       const float ell = t * softplusf_(-x) + (1.0f - t) * softplusf_(x);
-      d_out[i] = gl * s * (px - t) * inv_s0;
+      d_out[i] = gl * s * dx * inv_s0;
       d_sel[i] = s * (1.0f - s) * (gl * (ell - R) * inv_s0 + cterm);
     }
   }
@@ -1325,7 +1334,7 @@ __global__ void bce_bwd_kernel(const float* __restrict__ a, const float* __restr
                                const float* g_loss, float* d) {
   const float g = g_loss ? g_loss[0] : 1.0f;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < P; i += (int64_t)gridDim.x * blockDim.x)
-    d[i] = g * (sigmoidf_(a[i]) - t[i]) * inv_p;
+    d[i] = g * sigmoid_minus_(a[i], t[i]) * inv_p;
 }
 
 // =========================================================================== N-output heads
@@ -1590,8 +1599,8 @@ __global__ void ce_bwd_kernel(const float* __restrict__ a, const int64_t* __rest
 }
 
 // =========================================================================== Adam
-__global__ void adam_kernel(const selunet_adam_tensor* __restrict__ list, int n, float lr_bc1, float beta1,
-                            float beta2, float eps, float wd, float bc2_sqrt) {
+__global__ void adam_kernel(const selunet_adam_tensor* __restrict__ list, int n, float lr_bc1, float w1,
+                            float beta2, float w2, float eps, float wd, float bc2_sqrt) {
   const int64_t chunk = blockIdx.x;
   int t = 0;
   while (t + 1 < n && list[t + 1].chunk_begin <= chunk) ++t;
@@ -1603,8 +1612,8 @@ __global__ void adam_kernel(const selunet_adam_tensor* __restrict__ list, int n,
     float p = T.param[i];
     if (wd != 0.0f) g += wd * p;
     float m = T.exp_avg[i];
-    m = m + (1.0f - beta1) * (g - m);  // exp_avg.lerp_(grad, 1 - beta1)
-    float v = T.exp_avg_sq[i] * beta2 + (1.0f - beta2) * g * g;
+    m = m + w1 * (g - m);  // exp_avg.lerp_(grad, 1 - beta1)
+    float v = T.exp_avg_sq[i] * beta2 + w2 * g * g;  // .mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
     const float denom = sqrtf(v) / bc2_sqrt + eps;
     p = p - lr_bc1 * (m / denom);
     T.exp_avg[i] = m;
@@ -2192,13 +2201,28 @@ int selunet_bce_bwd(const float* logit, const float* target, int64_t p, double p
   return check_launch("bce_bwd");
 }
 
+// The double a caller rounded to the fp32 `v` of this ABI: the shortest decimal that rounds to the same fp32
+// (0.999f -> 0.999; a value that needs all 9 digits is its own fp32).
+static double short_decimal(float v) {
+  char buf[32];
+  for (int digits = 1; digits <= 9; ++digits) {
+    snprintf(buf, sizeof(buf), "%.*g", digits, (double)v);
+    if (std::strtof(buf, nullptr) == v) return std::strtod(buf, nullptr);
+  }
+  return (double)v;
+}
+
 int selunet_adam_step(const selunet_adam_tensor* list, int32_t n, int64_t total_chunks, float lr, float beta1,
                       float beta2, float eps, float weight_decay, int64_t step, void* stream) {
   SELUNET_REQUIRE(list && n > 0 && total_chunks > 0 && step > 0, "adam_step: bad arguments");
-  const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
+  // torch forms 1 - beta and the bias corrections in double from the Python floats (0.9, 0.999) and rounds the
+  // results to fp32: 1.0f - 0.999f is 1.3e-5 off (float)(1 - 0.999), and exp_avg_sq by as much
+  const double b1 = short_decimal(beta1), b2 = short_decimal(beta2);
+  const double bc1 = 1.0 - std::pow(b1, (double)step);
+  const double bc2 = 1.0 - std::pow(b2, (double)step);
   hipLaunchKernelGGL(adam_kernel, dim3((unsigned)total_chunks), dim3(TPB), 0, as_stream(stream), list, n,
-                     (float)(lr / bc1), beta1, beta2, eps, weight_decay, (float)std::sqrt(bc2));
+                     (float)(lr / bc1), (float)(1.0 - b1), beta2, (float)(1.0 - b2), eps, weight_decay,
+                     (float)std::sqrt(bc2));
   return check_launch("adam_step");
 }
 
