@@ -71,6 +71,11 @@ enum {
                                    * bf16: K >= 512): the LDS-DMA ring kernels with the forward on 8 x 1 waves (2,
                                    * default) or, fp32, 4 x 2 waves (1), or the resident-weight / staged kernels (0);
                                    * selunet_gemm_gather_x2_stats_rows / selunet_gemm_stats_rows follow it */
+  SELUNET_OPT_IO_GRID,            /* grid-stride I/O, metrics and prediction launches: upper bound on the workgroup
+                                   * count; default each launcher's own cap. For tests and small inputs: the kernels'
+                                   * per-workgroup 32-bit partial counts are sized for the default grids (a small grid
+                                   * on more than 2^30 pixels can overflow them), and a value above a launcher's own cap
+                                   * raises that cap */
   SELUNET_OPT_COUNT
 };
 /* Sets option `key` to `value` (< 0: default); returns the previous setting, or INT64_MIN for an

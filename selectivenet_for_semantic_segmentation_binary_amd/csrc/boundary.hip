@@ -265,8 +265,9 @@ int selunet_boundary_bands(const float* out, const float* sel, const float* targ
                   "boundary_bands: inputs must be 16-B aligned");
   SELUNET_REQUIRE(((uintptr_t)bins & 7) == 0, "boundary_bands: bins must be 8-B aligned");
   const int64_t p = (int64_t)n * hw;
-  // p <= 2^40 over at least min(p / 1024, 2048) workgroups: a 32-bit LDS count stays below 2^30
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(p / 4 + 1, BND_TPB), 2048));
+  // p <= 2^40 over at least min(p / 1024, 2048) workgroups: a 32-bit LDS count stays below 2^30 (at the default
+  // grid; SELUNET_OPT_IO_GRID can make it smaller and is for tests and small inputs only, see selunet.h)
+  const unsigned grid = (unsigned)io_grid(cdiv(p / 4 + 1, BND_TPB), 2048);
   hipLaunchKernelGGL(boundary_bands_kernel, dim3(grid), dim3(BND_TPB), 0, as_stream(stream), out, sel, target,
                      d2_target, p, t_out, t_sel, e, bins);
   return check_launch("boundary_bands");
@@ -286,7 +287,7 @@ int selunet_boundary_rows(const float* out, const float* sel, const float* targe
                    mask) == 0,
                   "boundary_rows: inputs must be 16-B aligned (4-B when hw is not a multiple of 4)");
   SELUNET_REQUIRE(((uintptr_t)rows & 7) == 0, "boundary_rows: rows must be 8-B aligned");
-  const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(hw / 4, BND_TPB * 4), 64));
+  const unsigned gx = (unsigned)io_grid(cdiv(hw / 4, BND_TPB * 4), 64);
   for (int32_t i0 = 0; i0 < n; i0 += BND_GRID_Y) {
     const int64_t o = (int64_t)i0 * hw;
     hipLaunchKernelGGL(boundary_rows_kernel, dim3(gx, (unsigned)std::min(n - i0, BND_GRID_Y)), dim3(BND_TPB), 0,

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -40,6 +41,13 @@ inline int64_t option(int key, int64_t dflt) { return g_options[key] < 0 ? dflt 
 int x2_tile_queue_prepare();
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Workgroups of a grid-stride I/O, metrics or prediction launch: the launcher's own rule `want` under its own cap,
+// or under SELUNET_OPT_IO_GRID where that is set (every such kernel strides by its gridDim, so any grid >= 1 does
+// the same work; the option is for tests and small inputs: 32-bit partial counts are sized for the default grids)
+inline int64_t io_grid(int64_t want, int64_t cap) {
+  return std::max<int64_t>(1, std::min<int64_t>(want, std::max<int64_t>(1, option(SELUNET_OPT_IO_GRID, cap))));
+}
 
 // ------------------------------------------------------------------ element access
 // 4 consecutive elements <-> float4 in registers.

@@ -129,7 +129,7 @@ int selunet_tile_gather(const uint8_t* img, int32_t h, int32_t w, const int32_t*
   SELUNET_REQUIRE(mode >= 0 && mode <= 2, "tile_gather: mode 0 'RGB', 1 'GH', 2 'H_RGB' (got %d)", mode);
   SELUNET_REQUIRE(((uintptr_t)x & 15) == 0, "tile_gather: x must be 16-B aligned");
   const int64_t total = (int64_t)n * th * (tw / 4);
-  const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(total, PRED_TPB), 8192)));
+  const dim3 grid((unsigned)io_grid(cdiv(total, PRED_TPB), 8192));
   auto kernel = mode == 0 ? tile_gather_kernel<3, false> : mode == 1 ? tile_gather_kernel<2, false>
                                                                      : tile_gather_kernel<3, true>;
   hipLaunchKernelGGL(kernel, grid, dim3(PRED_TPB), 0, as_stream(stream), img, h, w, origins, n, th, tw, x);
@@ -158,7 +158,7 @@ int selunet_tile_stitch(const float* out, const float* sel, const int32_t* origi
   const int64_t total = (int64_t)n * (th - 2 * halo) * ((tw - 2 * halo) / 8);
   SELUNET_REQUIRE(total * 8 < ((int64_t)1 << 32), "tile_stitch: %lld core pixels in one call, at most 2^32 - 1",
                   (long long)total * 8);
-  const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(cdiv(total, PRED_TPB), 2048));
+  const int64_t blocks = io_grid(cdiv(total, PRED_TPB), 2048);
   hipLaunchKernelGGL(tile_stitch_kernel, dim3((unsigned)blocks), dim3(PRED_TPB), 0, as_stream(stream), out, sel, origins,
                      n, th, tw, halo, h, w, hc, wc, t_out, t_sel, logit_plane, sel_plane, mask, prob8, counts);
   return check_launch("tile_stitch");

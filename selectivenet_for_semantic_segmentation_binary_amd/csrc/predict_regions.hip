@@ -474,7 +474,7 @@ __global__ __launch_bounds__(PRED_TPB) void regions_apply_kernel(uint8_t* __rest
 }
 
 static int64_t grid_for(int64_t threads) {
-  return std::max<int64_t>(1, std::min<int64_t>(cdiv(threads, PRED_TPB), 16384));
+  return io_grid(cdiv(threads, PRED_TPB), 16384);
 }
 
 // The rules every call shares: the image's size, and the pitched label plane that goes with it.

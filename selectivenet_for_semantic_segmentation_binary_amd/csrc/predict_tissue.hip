@@ -154,7 +154,7 @@ int selunet_tissue_plane(const uint8_t* img, int32_t h, int32_t w, int32_t brigh
                   w);
   SELUNET_REQUIRE(((uintptr_t)plane & 3) == 0, "tissue_plane: plane must be 4-B aligned");
   const int64_t total = (int64_t)h * (pitch / 4);
-  const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(cdiv(total, PRED_TPB), 8192));
+  const int64_t blocks = io_grid(cdiv(total, PRED_TPB), 8192);
   hipLaunchKernelGGL(tissue_plane_kernel, dim3((unsigned)blocks), dim3(PRED_TPB), 0, as_stream(stream), img, h, w,
                      bright, spread, plane, pitch);
   return check_launch("tissue_plane");
@@ -188,7 +188,7 @@ int selunet_tissue_class_counts(const uint8_t* mask, int64_t mask_pitch, const u
   SELUNET_REQUIRE(((uintptr_t)counts & 7) == 0, "tissue_class_counts: counts must be 8-B aligned");
   // the per-thread and per-wave partial counts are 32 bits wide; H W < 2^32 by the bound above
   const int64_t total = (int64_t)h * ((w + 3) / 4);
-  const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(cdiv(total, PRED_TPB), 2048));
+  const int64_t blocks = io_grid(cdiv(total, PRED_TPB), 2048);
   hipLaunchKernelGGL(tissue_class_counts_kernel, dim3((unsigned)blocks), dim3(PRED_TPB), 0, as_stream(stream), mask,
                      mask_pitch, plane, pitch, h, w, counts);
   return check_launch("tissue_class_counts");

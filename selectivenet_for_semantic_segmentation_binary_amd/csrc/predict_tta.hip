@@ -282,7 +282,7 @@ int selunet_tile_gather_flip(const uint8_t* img, int32_t h, int32_t w, const int
                   flip);
   SELUNET_REQUIRE(aligned16(x), "tile_gather_flip: x must be 16-B aligned");
   const int64_t total = (int64_t)n * th * (tw / 4);
-  const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(total, PRED_TPB), 8192)));
+  const dim3 grid((unsigned)io_grid(cdiv(total, PRED_TPB), 8192));
   auto kernel = mode == 0 ? tile_gather_flip_kernel<3, false> : mode == 1 ? tile_gather_flip_kernel<2, false>
                                                                           : tile_gather_flip_kernel<3, true>;
   hipLaunchKernelGGL(kernel, grid, dim3(PRED_TPB), 0, as_stream(stream), img, h, w, origins, n, th, tw, flip, x);
@@ -319,7 +319,7 @@ int selunet_tta_accumulate(const float* out, const float* sel, const int32_t* or
   SELUNET_REQUIRE(aligned16(out) && aligned16(sel) && aligned16(sum_out) && aligned16(sum_sel) && aligned16(votes) &&
                       aligned16(sel_votes), "tta_accumulate: tiles and planes must be 16-B aligned");
   const int64_t total = (int64_t)n * (th - 2 * halo) * ((tw - 2 * halo) / 8 + 1);
-  const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(cdiv(total, PRED_TPB), 8192));
+  const int64_t blocks = io_grid(cdiv(total, PRED_TPB), 8192);
   hipLaunchKernelGGL(tta_accumulate_kernel, dim3((unsigned)blocks), dim3(PRED_TPB), 0, as_stream(stream), out, sel,
                      origins, n, th, tw, halo, flip, first, h, w, ws, t_out, t_sel, sum_out, sum_sel, votes, sel_votes);
   return check_launch("tta_accumulate");

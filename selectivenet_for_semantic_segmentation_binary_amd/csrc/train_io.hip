@@ -423,7 +423,7 @@ int selunet_prep_batch_mode(const uint8_t* img, const uint8_t* lab, const uint8_
   SELUNET_REQUIRE(img && lab && x && target && n > 0 && h > 0 && w > 0 && w % 4 == 0, "prep_batch: bad arguments");
   SELUNET_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)target & 15) == 0, "prep_batch: outputs must be 16-B aligned");
   const int64_t total = (int64_t)n * h * (w / 4);
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(total, IO_TPB), 8192));
+  const unsigned grid = (unsigned)io_grid(cdiv(total, IO_TPB), 8192);
   hipLaunchKernelGGL((prep_batch_kernel<3, true>), dim3(grid), dim3(IO_TPB), 0, as_stream(stream), img, lab, flips, n, h,
                      w, x, target);
   return check_launch("prep_batch");
@@ -436,7 +436,7 @@ int selunet_prep_batch(const uint8_t* img, const uint8_t* lab, const uint8_t* fl
   SELUNET_REQUIRE(w % 4 == 0, "prep_batch: width must be a multiple of 4");
   SELUNET_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)target & 15) == 0, "prep_batch: outputs must be 16-B aligned");
   const int64_t total = (int64_t)n * h * (w / 4);
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(total, IO_TPB), 8192));
+  const unsigned grid = (unsigned)io_grid(cdiv(total, IO_TPB), 8192);
   hipLaunchKernelGGL(cin == 3 ? prep_batch_kernel<3> : prep_batch_kernel<2>, dim3(grid), dim3(IO_TPB), 0,
                      as_stream(stream), img, lab, flips, n, h, w, x, target);
   return check_launch("prep_batch");
@@ -447,7 +447,7 @@ int selunet_seg_metrics(const float* out, const float* sel, const float* target,
   SELUNET_REQUIRE(out && target && counts && p > 0, "seg_metrics: bad arguments");
   SELUNET_REQUIRE(((uintptr_t)out & 15) == 0 && ((uintptr_t)target & 15) == 0 && ((uintptr_t)sel & 15) == 0,
                   "seg_metrics: inputs must be 16-B aligned");
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(p / 4 + 1, IO_TPB), 2048));
+  const unsigned grid = (unsigned)io_grid(cdiv(p / 4 + 1, IO_TPB), 2048);
   hipLaunchKernelGGL(seg_metrics_kernel, dim3(grid), dim3(IO_TPB), 0, as_stream(stream), out, sel, target, p, t_out,
                      t_sel, counts);
   return check_launch("seg_metrics");
@@ -470,7 +470,7 @@ int selunet_seg_metrics_rows(const float* out, const float* sel, const float* ta
                              float t_out, float t_sel, unsigned long long* rows, void* stream) {
   if (int rc = patch_rows_args("seg_metrics_rows", out, sel, target, n, hw, rows)) return rc;
   // at least four 16-B loads per thread before a workgroup's five closing atomics
-  const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(hw / 4, IO_TPB * 4), 64));
+  const unsigned gx = (unsigned)io_grid(cdiv(hw / 4, IO_TPB * 4), 64);
   for (int32_t i0 = 0; i0 < n; i0 += PATCH_GRID_Y) {  // a grid's y dimension is 16 bits wide
     const int64_t o = (int64_t)i0 * hw;
     hipLaunchKernelGGL(seg_metrics_rows_kernel, dim3(gx, (unsigned)std::min(n - i0, PATCH_GRID_Y)), dim3(IO_TPB), 0,

@@ -98,6 +98,36 @@ def clean(mask, prob8=None, min_region=0, fill_holes=0, connectivity=8):
     return m, table(m, label(m, 255, connectivity), prob8), counts(m), done
 
 
+# ----------------------------------------------------------------------------- labels without a flood fill
+ONE_PATH = ("spiral", "serpentine", "comb")  # a single region under either connectivity, (0, 0) its first pixel
+
+
+def analytic_labels(name, mask, connectivity):
+    """The labels of the 255-regions of pattern `name`, known without a search (tests/test_io_regimes_host.py holds
+    them against label() at 70 x 130): (0, 0) is set in all four patterns; spiral, serpentine and comb are one
+    region under 4 and under 8, the checkerboard is one region under 8 (every set pixel touches the next
+    diagonally), and under 4 every set pixel of it is a region of its own, 1 + y W + x."""
+    assert name in ONE_PATH + ("checkerboard",) and connectivity in (4, 8) and mask[0, 0] == 255
+    H, W = mask.shape
+    hit = mask == 255
+    if name == "checkerboard" and connectivity == 4:
+        own = 1 + np.arange(H, dtype=np.int64)[:, None] * W + np.arange(W, dtype=np.int64)[None, :]
+        return np.where(hit, own, 0).astype(np.int32)
+    return hit.astype(np.int32)
+
+
+def canonical(lab):
+    """Any labelling (0 = background, one positive integer per region, scipy.ndimage.label's for instance) renamed
+    to 1 + the raster index of each region's first pixel."""
+    lab = np.asarray(lab)
+    flat = lab.reshape(-1)
+    pos = np.flatnonzero(flat)
+    names, first = np.unique(flat[pos], return_index=True)  # the first occurrence in raster order
+    rename = np.zeros(int(flat.max()) + 1, np.int64)
+    rename[names] = 1 + pos[first]
+    return rename[flat].reshape(lab.shape).astype(np.int32)
+
+
 # ----------------------------------------------------------------------------- patterns
 def checkerboard(H, W):
     return (((np.arange(H)[:, None] + np.arange(W)[None, :]) % 2 == 0) * 255).astype(np.uint8)
