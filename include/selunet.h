@@ -781,6 +781,47 @@ int selunet_boundary_rows(const float* out, const float* sel, const float* targe
                           const int32_t* d2_pred, int32_t n, int64_t hw, float t_out, float t_sel,
                           int32_t tol_sq, unsigned long long* rows, void* stream);
 
+/* ---- calibration report ---------------------------------------------------------
+ * Can a score be read as a probability: the reliability histogram of sigmoid(score / T) against an
+ * event, with the sums behind the Brier score and the NLL, and a fine histogram of the raw score for a
+ * temperature fit. Integer counts, fixed-point integer sums and integer atomics only: every result is
+ * the same bit for bit on every run.
+ * score / out / sel / target: fp32 [p] (out nullable with event 0, sel nullable; they may alias).
+ * With label = (int)(uint8_t)target, a pixel is considered when label < 2, it is selected (sel == NULL
+ * or sel >= t_sel) and score is not NaN (the rules of selunet_seg_metrics and selunet_patch_auc);
+ * selected pixels with label < 2 and a NaN score are counted in misc[0] only, selected pixels with
+ * label >= 2 in misc[1] only (misc: uint64 [2], caller-zeroed, accumulated).
+ * The event e of a considered pixel: event 0: e = label; event 1: e = ((out >= t_out) == (label == 1)),
+ * "the prediction is right".
+ * Its reliability bin b = #{j < m : score >= edges[j]} on the raw score (edges: DEVICE array, ascending
+ * — the caller's duty —, duplicates and +-inf allowed, 1 <= m <= SELUNET_CALIB_MAX_EDGES; the caller
+ * folds any temperature into the edges).
+ * Its values, in fp64: x = (double)score * inv_temperature,
+ *   s = x >= 0 ? 1 / (1 + exp(-x)) : exp(x) / (1 + exp(x)),
+ *   P = llrint(s * 2^FRAC_BITS), B = llrint((s - e)^2 * 2^FRAC_BITS),
+ *   L = llrint(min(softplus(e ? -x : x), NLL_MAX) * 2^NLL_BITS), softplus(v) = max(v, 0) + log1p(exp(-|v|));
+ * +-inf scores are ordinary values (s is exactly 0 or 1, a wrong one costs the capped NLL_MAX nats).
+ * bins: uint64 [(m + 1)][5], caller-zeroed, accumulated across calls: bins[b] += {1 - e, e, P, B, L}.
+ * fine (nullable): uint64 [SELUNET_CALIB_FINE_CELLS][2], caller-zeroed, accumulated: fine[cell][e] += 1 with
+ *   cell 0 for score < -32, cell 4097 for score >= 32, else 2049 + (int)floorf(score * 64.0f) (the fp32
+ *   product is exact).
+ * The sums are sized for 2^33 accumulated pixels (2^33 * 2^30 < 2^64): keeping the accumulated total below
+ * it is the caller's duty. Per launch a workgroup counts about p / 256 <= 2^25 pixels into a 32-bit
+ * on-chip counter of `fine`; the on-chip sums of `bins` are 64 bits wide.
+ * EINVAL (before any device call): a null pointer where one is required; p < 1 or p > 2^33; event outside
+ * {0, 1}; m out of range; inv_temperature not finite or not > 0; score / out / sel / target not 16-B
+ * aligned, edges not 4-B aligned, bins / fine / misc not 8-B aligned. */
+#define SELUNET_CALIB_MAX_EDGES 255
+#define SELUNET_CALIB_FRAC_BITS 30
+#define SELUNET_CALIB_NLL_BITS 20
+#define SELUNET_CALIB_NLL_MAX 1024
+#define SELUNET_CALIB_FINE_CELLS 4098
+int selunet_calibration_bins(const float* score, const float* out, const float* sel, const float* target,
+                             int64_t p, int32_t event, float t_out, float t_sel,
+                             const float* edges, int32_t m, double inv_temperature,
+                             unsigned long long* bins, unsigned long long* fine,
+                             unsigned long long* misc, void* stream);
+
 /* ---- whole-image prediction I/O --------------------------------------------
  * A trained network applied to an image of any size: overlapping tiles are gathered from the image, run
  * through the eval-mode forward, and the tiles' cores (tile minus a halo on every side) stitched into

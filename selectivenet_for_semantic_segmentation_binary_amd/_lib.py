@@ -27,6 +27,11 @@ AUC_CHUNK = 4096  # SELUNET_AUC_CHUNK
 EDT_NONE = 2 ** 31 - 1  # SELUNET_EDT_NONE
 EDT_MAX_SIDE = 4096  # SELUNET_EDT_MAX_SIDE
 BAND_MAX = 15  # SELUNET_BAND_MAX
+CALIB_MAX_EDGES = 255  # SELUNET_CALIB_MAX_EDGES
+CALIB_FRAC_BITS = 30  # SELUNET_CALIB_FRAC_BITS
+CALIB_NLL_BITS = 20  # SELUNET_CALIB_NLL_BITS
+CALIB_NLL_MAX = 1024  # SELUNET_CALIB_NLL_MAX
+CALIB_FINE_CELLS = 4098  # SELUNET_CALIB_FINE_CELLS
 EDT_ROW_CHUNK = 256  # pixels of a row one sweep of the EDT row pass's workgroup takes (csrc/boundary.hip)
 
 
@@ -207,6 +212,8 @@ SIGNATURES = {
     "selunet_boundary_bands": (c_int32, [P, P, P, P, c_int32, c_int64, c_float, c_float, ctypes.POINTER(c_int32),
                                          c_int32, P, P]),
     "selunet_boundary_rows": (c_int32, [P, P, P, P, P, c_int32, c_int64, c_float, c_float, c_int32, P, P]),
+    "selunet_calibration_bins": (c_int32, [P, P, P, P, c_int64, c_int32, c_float, c_float, P, c_int32, c_double, P, P,
+                                           P, P]),
     "selunet_tile_gather": (c_int32, [P, c_int32, c_int32, P, c_int32, c_int32, c_int32, c_int32, P, P]),
     "selunet_tile_stitch": (c_int32, [P, P, P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                       c_float, c_float, P, P, P, P, P, P]),

@@ -28,6 +28,13 @@ prediction masks, the Evaluator's counts, coverage and risk by band of distance 
 (--boundary_bands R [R ...], default 1 2 4 8 16) in boundary_bands.json / .csv, and per patch the Hausdorff
 distance and the scores that forgive errors within --boundary_tolerance T (default 2) pixels of the other mask
 in patch_boundary.csv, with a summary in patch_boundary.json. Over the selected pixels with --select_eval.
+Calibration report (MI355X path only): --calibration_report 1 asks whether the scores can be read as probabilities,
+from the same pass (`metrics.CalibrationReport`, DESIGN.md §7k): per view (tumor; tumor_selected with --select_eval;
+selection — the selection score against "the prediction is right" — with --selective) the reliability table over
+--calibration_bins K (default 20, even, 2..256) equal-width probability bins, ECE, top-label ECE, MCE, Brier score
+and NLL, and the temperature that minimises the NLL, in calibration.json and calibration_bins.csv;
+--calibration_temperature T (default 1) reports the tumor views of sigmoid(logit / T), so a fitted T can be checked
+by a second run. The outputs must be logits: --single_scale sigmoid, and --ens_scale None for an ensemble.
 fp32 conv path (MI355X path only): --fp32_path split runs the fp32 forward on the training forward's
 split-fp16 kernels (`UNet_B(fp32_eval_path="split")`); the default, exact, keeps the exact
 fp32 kernels. Not with --compute_dtype bf16.
@@ -88,7 +95,23 @@ def parse_arguments(argv=None):
     parser.add_argument('--boundary_tolerance', type=float, default=2,
                         help='errors within this distance (pixels) of the other mask count as correct in the '
                              'tolerant scores')
+    parser.add_argument('--calibration_report', type=bool, default=False,
+                        help='reliability table, ECE, Brier score, NLL and a temperature fit of the scores '
+                             '(calibration.json, calibration_bins.csv)')
+    parser.add_argument('--calibration_bins', type=int, default=20,
+                        help='equal-width probability bins of the reliability table: even, 2..256')
+    parser.add_argument('--calibration_temperature', type=float, default=1.0,
+                        help='report the tumor views of sigmoid(logit / T) (the fitted T of an earlier run)')
     args = parser.parse_args(argv)
+    if args.calibration_report:
+        if not 2 <= args.calibration_bins <= 256 or args.calibration_bins % 2:
+            parser.error('--calibration_bins: an even number of bins in [2, 256]')
+        if not 0 < args.calibration_temperature < float('inf'):
+            parser.error('--calibration_temperature: a finite temperature > 0')
+    else:
+        # off: as the boundary flags below
+        for name in ('calibration_report', 'calibration_bins', 'calibration_temperature'):
+            delattr(args, name)
     if args.boundary_report:
         from . import metrics as MT
         try:
@@ -141,6 +164,13 @@ def evaluate(args):
     cut_offs = sweep_cut_offs(args)
     if cut_offs is not None and not args.selective:
         raise ValueError("a selection cut-off sweep needs a selective network (--selective 1)")
+    if getattr(args, "calibration_report", False):  # the report reads the outputs as logits
+        if args.single_scale != 'sigmoid':
+            raise ValueError(f"--calibration_report needs --single_scale sigmoid (got {args.single_scale!r}): "
+                             "the outputs are read as logits")
+        if args.ens_scale != 'None' and len([c for c in os.listdir(args.model_dir) if 'pth' in c]) > 1:
+            raise ValueError(f"--calibration_report with an ensemble needs --ens_scale None (got {args.ens_scale!r}): "
+                             "a mean of logits is a logit, a mean of scaled outputs is not")
     device = torch.device("cuda", args.local_rank[0])
     torch.cuda.set_device(device)
     dt = torch.bfloat16 if args.compute_dtype == 'bf16' else torch.float32
@@ -175,6 +205,11 @@ def evaluate(args):
         boundary = MT.BoundaryReport(device, selective=bool(args.select_eval), radii=args.boundary_bands,
                                      tolerance=args.boundary_tolerance, rule="eval", cut_off=args.cut_off,
                                      s_cut_off=args.s_cut_off, output_scale=args.single_scale)
+    calibration = None
+    if getattr(args, "calibration_report", False):
+        calibration = MT.CalibrationReport(device, selective=bool(args.selective), select_eval=bool(args.select_eval),
+                                           bins=args.calibration_bins, temperature=args.calibration_temperature,
+                                           cut_off=args.cut_off, s_cut_off=args.s_cut_off)
     seen = 0  # patches fed so far: the loader walks the set in order
     print("Model Prediction...")
     with torch.no_grad():
@@ -211,7 +246,9 @@ def evaluate(args):
                 report.add_batch(output, target, selection, ids=ids)
             if boundary is not None:
                 boundary.add_batch(output, target, selection, ids=ids)
-    cm = ev.confusion_matrix()
+            if calibration is not None:
+                calibration.add_batch(output, target, selection)
+    cm =ev.confusion_matrix()
     selected, total = ev.selected_total()
     prec, rec = MT.precision(cm), MT.recall(cm)
     with np.errstate(invalid="ignore", divide="ignore"):
@@ -240,12 +277,38 @@ def evaluate(args):
     if boundary is not None:
         res = dict(res, boundary_report=report_boundary(boundary.bands(), boundary.rows(), boundary.radii,
                                                         boundary.tolerance, args.save_dir))
+    if calibration is not None:
+        res = dict(res, calibration_report=report_calibration(calibration.report(), args.save_dir))
     return res
 
 
 def _cell(v):
     """A CSV cell: integers as integers, floats by repr."""
     return repr(v) if isinstance(v, float) else str(v)
+
+
+def report_calibration(doc, save_dir):
+    """Print one line per view of `metrics.CalibrationReport.report()` and write calibration.json (the whole
+    document) and calibration_bins.csv (one row per view and reliability bin)."""
+    from . import metrics as MT
+
+    print(f'    calibration report ({doc["bins"]} bins):')
+    print('    ' + f'{"view":>14} {"pixels":>12} ' + ' '.join(
+        f'{c:>10}' for c in ("ECE", "top ECE", "MCE", "Brier", "NLL", "fitted T", "NLL at T")))
+    for name, v in doc["views"].items():
+        s, f = v["summary"], v["fit"]
+        print('    ' + f'{name:>14} {s["pixels"]:12d} ' + ' '.join(
+            f'{x:10.6f}' for x in (s["ece"], s["top_label_ece"], s["mce"], s["brier"], s["nll"], f["temperature"],
+                                   f["nll_fitted"])))
+    os.makedirs(save_dir, exist_ok=True)
+    with open(os.path.join(save_dir, "calibration.json"), "w") as fh:
+        json.dump(doc, fh, indent=1)
+    with open(os.path.join(save_dir, "calibration_bins.csv"), "w") as fh:
+        fh.write(",".join(("view",) + MT.CALIBRATION_BIN_COLUMNS) + "\n")
+        for name, v in doc["views"].items():
+            for r in v["table"]:
+                fh.write(",".join([name] + [_cell(r[c]) for c in MT.CALIBRATION_BIN_COLUMNS]) + "\n")
+    return doc
 
 
 def report_boundary(bands, rows, radii, tolerance, save_dir):

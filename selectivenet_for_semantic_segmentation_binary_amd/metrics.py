@@ -26,6 +26,13 @@ prediction logit, from which `patch_performance` forms the reference's unused `g
 of the label and prediction masks (`selunet_edt_sq`), the `SegMetrics` counts by band of distance to the
 label contour (`band_table`: where the network errs and abstains) and per patch the directed Hausdorff
 distances and boundary-tolerant scores (`boundary_patch`).
+
+`CalibrationReport` asks whether the scores can be read as probabilities: per view one
+`selunet_calibration_bins` call per batch counts the reliability bins of sigmoid(score / T) against an event with
+the fixed-point sums behind the Brier score and the NLL, and a fine histogram of the raw score; on the host,
+`calibration_edges` places the bins' logit thresholds by the reference's fp32 rule, `calibration_table` /
+`calibration_summary` form the table, ECE, top-label ECE, MCE, Brier score and NLL, and `fit_temperature` finds
+the temperature that minimises `nll_from_fine`.
 """
 from __future__ import annotations
 
@@ -594,3 +601,234 @@ def boundary_report_summary(rows) -> dict:
         doc[prefix + "mean_hausdorff"] = float(finite.mean()) if len(finite) else float("nan")
         doc[prefix + "median_hausdorff"] = float(np.median(finite)) if len(finite) else float("nan")
     return doc
+
+
+# ----------------------------------------------------------------------------- calibration
+CALIBRATION_BIN_COLUMNS = ("bin", "lo", "hi", "non_events", "events", "sum_score", "sum_brier", "sum_nll", "n",
+                           "event_rate", "mean_score", "gap")
+CALIBRATION_VIEWS = ("tumor", "tumor_selected", "selection")
+_FRAC = float(1 << K.CALIB_FRAC_BITS)
+_NLL = float(1 << K.CALIB_NLL_BITS)
+
+
+def calibration_edges(k, temperature: float = 1.0):
+    """(the k - 1 interior edges j / k of k equal-width probability bins, their fp32 logit thresholds): the
+    smallest fp32 score x whose probability reaches past the edge by the reference's fp32 rule,
+    `1/(1+exp(-(x/T))) > j/k`. At temperature 1 these are `sweep_thresholds(..., rule="eval")`, so the middle
+    edge is `logit_threshold("eval", 0.5)` and the bins line up with the Evaluator's prediction. k is even
+    (the top-label fold pairs bin k/2 + j with bin k/2 - 1 - j) and in [2, 256]. Pure host code."""
+    if isinstance(k, bool) or int(k) != k or not 2 <= int(k) <= K.CALIB_MAX_EDGES + 1 or int(k) % 2:
+        raise ValueError(f"calibration: the number of bins must be even and in [2, {K.CALIB_MAX_EDGES + 1}], got {k}")
+    k, t = int(k), float(temperature)
+    if not np.isfinite(t) or not t > 0:
+        raise ValueError(f"calibration: the temperature must be finite and > 0, got {temperature}")
+    cuts = [j / k for j in range(1, k)]
+    if t == 1.0:
+        return sweep_thresholds(cuts, rule="eval")
+    t32 = np.float32(t)
+    with np.errstate(over="ignore"):
+        thr = np.array([_bisect(lambda x, c=c: bool((1 / (1 + np.exp(-(np.array([x], np.float32) / t32)))) > c))
+                        for c in cuts], np.float32)
+    if np.any(thr[1:] < thr[:-1]):
+        raise ValueError(f"calibration: the logit thresholds at temperature {t} are not non-decreasing: {thr}")
+    return cuts, thr
+
+
+def _calibration_rows(rows):
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.shape[1] != 5 or rows.shape[0] < 2 or rows.shape[0] % 2:
+        raise ValueError(f"calibration: rows of shape {rows.shape}, expected [k][5] with k even")
+    return [[int(v) for v in r] for r in rows]  # Python integers: sums of 2^33 pixels x 2^30 pass 2^63
+
+
+def calibration_table(rows, k) -> list:
+    """One row per reliability bin from the [k][5] words {non-events, events, sum P, sum B, sum L} of
+    `selunet_calibration_bins`: the bin's probability range lo = b/k, hi = (b+1)/k, n = events + non-events,
+    event_rate = events / n, mean_score = sum P / 2^30 / n, gap = event_rate - mean_score (NaN for an empty bin)."""
+    rows = _calibration_rows(rows)
+    if len(rows) != k:
+        raise ValueError(f"calibration_table: {len(rows)} rows for {k} bins")
+    table = []
+    for b, (n0, n1, sp, sb, sl) in enumerate(rows):
+        n = n0 + n1
+        rate, mean = _ratio(n1, n), _ratio(sp / _FRAC, n)
+        table.append({"bin": b, "lo": b / k, "hi": (b + 1) / k, "non_events": n0, "events": n1, "sum_score": sp,
+                      "sum_brier": sb, "sum_nll": sl, "n": n, "event_rate": rate, "mean_score": mean,
+                      "gap": rate - mean})
+    return table
+
+
+def calibration_summary(rows) -> dict:
+    """pixels N; ECE = sum n_b / N |event_rate - mean_score| and MCE, the largest such gap of a non-empty bin;
+    Brier = sum B / 2^30 / N; NLL = sum L / 2^20 / N (nats, a pixel capped at 1024); and the top-label view,
+    the fold of bin k/2 + j with bin k/2 - 1 - j into confidence bin j (confidence in [1/2 + j/k, 1/2 + (j+1)/k]):
+    its confidence sum is P above the middle and n 2^30 - P below, its hits are the events above and the
+    non-events below; top_label_accuracy their share of N. NaN throughout without a pixel."""
+    rows = _calibration_rows(rows)
+    k = len(rows)
+    total = sum(r[0] + r[1] for r in rows)
+    ece, mce = 0.0, 0.0
+    for n0, n1, sp, _, _ in rows:
+        if n0 + n1:
+            gap = abs(n1 / (n0 + n1) - sp / _FRAC / (n0 + n1))
+            ece += (n0 + n1) / total * gap
+            mce = max(mce, gap)
+    top, top_ece, hits = [], 0.0, 0
+    for j in range(k // 2):
+        (u0, u1, up, _, _), (l0, l1, lp, _, _) = rows[k // 2 + j], rows[k // 2 - 1 - j]
+        n, correct = u0 + u1 + l0 + l1, u1 + l0
+        conf = up + ((l0 + l1) << K.CALIB_FRAC_BITS) - lp
+        acc, mean = _ratio(correct, n), _ratio(conf / _FRAC, n)
+        top.append({"bin": j, "lo": 0.5 + j / k, "hi": 0.5 + (j + 1) / k, "n": n, "correct": correct,
+                    "sum_confidence": conf, "accuracy": acc, "mean_confidence": mean, "gap": acc - mean})
+        if n:
+            top_ece += n / total * abs(acc - mean)
+        hits += correct
+    nan = float("nan")
+    return {"pixels": total, "ece": ece if total else nan, "mce": mce if total else nan,
+            "brier": _ratio(sum(r[3] for r in rows) / _FRAC, total), "nll": _ratio(sum(r[4] for r in rows) / _NLL, total),
+            "top_label_ece": top_ece if total else nan, "top_label_accuracy": _ratio(hits, total), "top_label": top}
+
+
+def fine_midpoints() -> np.ndarray:
+    """The score that stands for each cell of the fine histogram: the midpoint (c - 2049 + 0.5) / 64 of cells
+    1..4096, and -32 / +32 for the two open end cells."""
+    x = (np.arange(K.CALIB_FINE_CELLS, dtype=np.float64) - 2049 + 0.5) / 64
+    x[0], x[-1] = -32.0, 32.0
+    return x
+
+
+def _fine(fine):
+    fine = np.asarray(fine)
+    if fine.shape != (K.CALIB_FINE_CELLS, 2):
+        raise ValueError(f"calibration: fine histogram of shape {fine.shape}, expected ({K.CALIB_FINE_CELLS}, 2)")
+    return fine.astype(np.float64)
+
+
+def _softplus(v):
+    return np.maximum(v, 0) + np.log1p(np.exp(-np.abs(v)))
+
+
+def nll_from_fine(fine, temperature: float = 1.0) -> float:
+    """Mean NLL (nats per pixel) of sigmoid(score / temperature) read off the fine histogram [4098][2]
+    (`fine[cell][event]`), every pixel standing at its cell's `fine_midpoints`. A midpoint is at most 1/128
+    from its score and softplus is 1-Lipschitz, so this is within 1 / (128 T) of the exact mean while no
+    |score| >= 32. NaN without a pixel."""
+    f = _fine(fine)
+    x = fine_midpoints() / float(temperature)
+    n = f.sum()
+    return float((f[:, 0] * _softplus(x) + f[:, 1] * _softplus(-x)).sum() / n) if n else float("nan")
+
+
+def fit_temperature(fine) -> dict:
+    """The temperature T = 1/a that minimises `nll_from_fine`, a in [1/64, 64]. The NLL is convex in a, so the
+    root of its derivative sum x (n sigmoid(a x) - n_1) is found by Newton steps kept inside a bracket
+    (bisected on log a where a step leaves it), run to a relative step below 1e-9; the end of the range where
+    the NLL is monotone over it. Returns the temperature, the NLL at T = 1 and at the fitted T (all NaN
+    without a pixel)."""
+    f = _fine(fine)
+    n = f.sum(1)
+    if not n.sum():
+        return {"temperature": float("nan"), "nll": float("nan"), "nll_fitted": float("nan")}
+    x = fine_midpoints()
+
+    def slope(a):
+        s = 0.5 * (1 + np.tanh(0.5 * a * x))  # sigmoid without overflow
+        return float((x * (n * s - f[:, 1])).sum()), float((x * x * n * s * (1 - s)).sum())
+
+    lo, hi = 1 / 64, 64.0
+    if slope(lo)[0] >= 0:
+        a = lo
+    elif slope(hi)[0] <= 0:
+        a = hi
+    else:
+        a = 1.0
+        for _ in range(200):
+            g, h = slope(a)
+            if g > 0:
+                hi = a
+            elif g < 0:
+                lo = a
+            else:
+                break
+            nxt = a - g / h if h > 0 else 0.0
+            if not lo < nxt < hi:
+                nxt = float(np.sqrt(lo * hi))
+            step, a = abs(nxt - a), nxt
+            if step <= 1e-9 * a:
+                break
+    return {"temperature": 1 / a, "nll": nll_from_fine(fine, 1.0), "nll_fitted": nll_from_fine(fine, 1 / a)}
+
+
+class CalibrationReport:
+    """Whether the scores can be read as probabilities, in the pass eval already makes: per batch
+    one `selunet_calibration_bins` call per view,
+      tumor:          sigmoid(output / temperature) against the label, over all pixels;
+      tumor_selected: the same over the selected pixels (with `select_eval`);
+      selection:      sigmoid(selection) against "the prediction is right", over all pixels, at temperature 1
+                      (with a selective network): does the selection score track correctness.
+    Nothing synchronises per batch; `raw()` copies once (and all-reduces across data-parallel ranks), `report()`
+    adds each view's `calibration_table`, `calibration_summary` and `fit_temperature`."""
+
+    def __init__(self, device, selective: bool, select_eval: bool, bins: int = 20, temperature: float = 1.0,
+                 cut_off: float = 0.5, s_cut_off: float = 0.5):
+        self.selective, self.select_eval = bool(selective), bool(select_eval)
+        if self.select_eval and not self.selective:
+            raise ValueError("CalibrationReport: select_eval needs a selective network")
+        self.k, self.temperature = int(bins), float(temperature)
+        self.views = ["tumor"] + (["tumor_selected"] if self.select_eval else []) + (
+            ["selection"] if self.selective else [])
+        _, tumor = calibration_edges(bins, temperature)
+        self._edges = {"tumor": torch.tensor(tumor, dtype=torch.float32, device=device)}
+        if self.selective:
+            self._edges["selection"] = torch.tensor(calibration_edges(bins)[1], dtype=torch.float32, device=device)
+        self.t_out = logit_threshold("eval", cut_off)
+        self.t_sel = logit_threshold("eval", s_cut_off)
+        # per view, uint64 bits: bins [k][5], fine [4098][2], misc [2]
+        self._words = self.k * 5 + K.CALIB_FINE_CELLS * 2 + 2
+        self.counts = torch.zeros(len(self.views), self._words, dtype=torch.int64, device=device)
+
+    def reset(self):
+        self.counts.zero_()
+
+    def view_temperature(self, view: str) -> float:
+        return 1.0 if view == "selection" else self.temperature
+
+    def add_batch(self, output: torch.Tensor, target: torch.Tensor, selection: torch.Tensor | None = None):
+        for name, t in (("output", output), ("target", target), ("selection", selection)):
+            if t is not None and (t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise RuntimeError(f"CalibrationReport.add_batch: {name} must be a contiguous cuda fp32 tensor")
+        if output.numel() != target.numel() or (selection is not None and selection.numel() != output.numel()):
+            raise ValueError("CalibrationReport.add_batch: output, target and selection must have the same size")
+        if self.selective and selection is None:
+            raise ValueError("selective CalibrationReport needs the selection logits")
+        stream = K.stream_ptr()
+        for i, view in enumerate(self.views):
+            if view == "selection":
+                score, out, sel, event, edges = selection, output, None, 1, self._edges["selection"]
+            else:
+                score, out, event, edges = output, None, 0, self._edges["tumor"]
+                sel = selection if view == "tumor_selected" else None
+            base = self.counts[i].data_ptr()
+            K.call("selunet_calibration_bins", K.ptr(score), K.ptr(out), K.ptr(sel), K.ptr(target), output.numel(),
+                   event, self.t_out, self.t_sel, K.ptr(edges), self.k - 1, 1.0 / self.view_temperature(view), base,
+                   base + self.k * 5 * 8, base + (self._words - 2) * 8, stream)
+
+    def raw(self) -> dict:
+        c = self.counts.clone()
+        parallel.allreduce_sums(c)
+        host = c.cpu().numpy().astype(np.int64)
+        at = self.k * 5
+        return {view: {"bins": host[i, :at].reshape(self.k, 5), "fine": host[i, at:-2].reshape(-1, 2),
+                       "misc": host[i, -2:]} for i, view in enumerate(self.views)}
+
+    def report(self) -> dict:
+        doc = {"bins": self.k, "views": {}}
+        for view, r in self.raw().items():
+            edges = self._edges["selection" if view == "selection" else "tumor"].cpu().numpy()
+            doc["views"][view] = {"temperature": self.view_temperature(view),
+                                  "edge_logits": [float(v) for v in edges],
+                                  "nan_scores": int(r["misc"][0]), "other_labels": int(r["misc"][1]),
+                                  "summary": calibration_summary(r["bins"]), "fit": fit_temperature(r["fine"]),
+                                  "table": calibration_table(r["bins"], self.k)}
+        return doc
