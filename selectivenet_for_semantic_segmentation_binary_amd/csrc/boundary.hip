@@ -14,6 +14,7 @@
 #include <climits>
 
 #include "common.h"
+#include "metrics_common.h"
 
 namespace selunet {
 
@@ -98,18 +99,11 @@ __global__ __launch_bounds__(EDT_ROW_TPB) void edt_rows_kernel(const float* __re
 }
 
 constexpr int BND_TPB = 256;
-constexpr int BND_STATES = 6;  // cm cells 0..3, selected with a label >= 2, not selected
+constexpr int BND_STATES = PIXEL_STATES;  // pixel_state (metrics_common.h): selunet_seg_metrics' pixel rule
 struct BandEdges {
   int32_t r2[SELUNET_BAND_MAX];
   int32_t k;
 };
-
-// selunet_seg_metrics' pixel rules as one of BND_STATES states
-__device__ __forceinline__ int bnd_state(float o, float s, float t, bool has_sel, float t_out, float t_sel) {
-  const int lab = (int)(uint8_t)t;
-  const bool selected = !has_sel || s >= t_sel;
-  return !selected ? 5 : lab >= 2 ? 4 : lab * 2 + (o >= t_out ? 1 : 0);
-}
 
 // One LDS histogram [band][state] per workgroup, one LDS atomic per pixel; the six words of a band
 // follow from its states at the end (selected = states 0..4, pixels = all six).
@@ -121,26 +115,13 @@ __global__ __launch_bounds__(BND_TPB) void boundary_bands_kernel(
   const int nb = e.k + 2;
   for (int i = threadIdx.x; i < nb * BND_STATES; i += BND_TPB) hist[i] = 0;
   __syncthreads();
-  auto one = [&](float o, float s, float t, int32_t d) {
+  auto one = [&](float o, float t, float s, int32_t d) {
     int b = 0;
     for (int j = 0; j < e.k; ++j) b += d > e.r2[j];
     if (d == SELUNET_EDT_NONE) b = e.k + 1;
-    atomicAdd(&hist[b * BND_STATES + bnd_state(o, s, t, sel != nullptr, t_out, t_sel)], 1u);
+    atomicAdd(&hist[b * BND_STATES + pixel_state(o, s, t, sel != nullptr, t_out, t_sel)], 1u);
   };
-  const int64_t p4 = p >> 2;
-  const int64_t stride = (int64_t)gridDim.x * BND_TPB;
-  for (int64_t i = blockIdx.x * (int64_t)BND_TPB + threadIdx.x; i < p4; i += stride) {
-    const f32x4 o = *reinterpret_cast<const f32x4*>(out + i * 4);
-    const f32x4 t = *reinterpret_cast<const f32x4*>(target + i * 4);
-    const f32x4 s = sel ? *reinterpret_cast<const f32x4*>(sel + i * 4) : f32x4{0, 0, 0, 0};
-    const int4 d = *reinterpret_cast<const int4*>(d2 + i * 4);
-    one(o[0], s[0], t[0], d.x);
-    one(o[1], s[1], t[1], d.y);
-    one(o[2], s[2], t[2], d.z);
-    one(o[3], s[3], t[3], d.w);
-  }
-  for (int64_t i = p4 * 4 + blockIdx.x * (int64_t)BND_TPB + threadIdx.x; i < p; i += stride)
-    one(out[i], sel ? sel[i] : 0.0f, target[i], d2[i]);
+  for_each_pixel<BND_TPB>(p, true, one, out, target, nullable(sel), d2);
   __syncthreads();
   for (int i = threadIdx.x; i < nb * 6; i += BND_TPB) {
     const unsigned* hb = hist + (i / 6) * BND_STATES;
@@ -165,8 +146,8 @@ __global__ __launch_bounds__(BND_TPB) void boundary_rows_kernel(
   if (sel) sel += base;
   unsigned mx[2] = {0, 0};  // distances are non-negative int32
   unsigned cnt[4] = {0, 0, 0, 0};
-  auto one = [&](float o, float s, float t, int32_t dt, int32_t dp) {
-    const int st = bnd_state(o, s, t, sel != nullptr, t_out, t_sel);
+  auto one = [&](float o, float t, float s, int32_t dt, int32_t dp) {
+    const int st = pixel_state(o, s, t, sel != nullptr, t_out, t_sel);
     if (st == 1) {  // label 0, predicted 1
       mx[0] = max(mx[0], (unsigned)dt);
       cnt[0] += dt <= tol_sq;
@@ -177,51 +158,14 @@ __global__ __launch_bounds__(BND_TPB) void boundary_rows_kernel(
       cnt[3] += 1;
     }
   };
-  const int64_t p4 = (hw & 3) ? 0 : hw >> 2;  // image bases are 16-B aligned only when hw % 4 == 0
-  const int64_t stride = (int64_t)gridDim.x * BND_TPB;
-  for (int64_t i = blockIdx.x * (int64_t)BND_TPB + threadIdx.x; i < p4; i += stride) {
-    const f32x4 o = *reinterpret_cast<const f32x4*>(out + i * 4);
-    const f32x4 t = *reinterpret_cast<const f32x4*>(target + i * 4);
-    const f32x4 s = sel ? *reinterpret_cast<const f32x4*>(sel + i * 4) : f32x4{0, 0, 0, 0};
-    const int4 dt = *reinterpret_cast<const int4*>(d2_target + i * 4);
-    const int4 dp = *reinterpret_cast<const int4*>(d2_pred + i * 4);
-    one(o[0], s[0], t[0], dt.x, dp.x);
-    one(o[1], s[1], t[1], dt.y, dp.y);
-    one(o[2], s[2], t[2], dt.z, dp.z);
-    one(o[3], s[3], t[3], dt.w, dp.w);
-  }
-  for (int64_t i = p4 * 4 + blockIdx.x * (int64_t)BND_TPB + threadIdx.x; i < hw; i += stride)
-    one(out[i], sel ? sel[i] : 0.0f, target[i], d2_target[i], d2_pred[i]);
-  __shared__ unsigned red[BND_TPB / 64][6];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    unsigned v = mx[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor(v, o, 64));
-    if (lane == 0) red[wave][k] = v;
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    unsigned v = cnt[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (lane == 0) red[wave][2 + k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    unsigned long long* word = rows + (int64_t)blockIdx.y * 6 + threadIdx.x;
-    unsigned long long v = 0;
-    for (int wv = 0; wv < BND_TPB / 64; ++wv)
-      v = threadIdx.x < 2 ? max(v, (unsigned long long)red[wv][threadIdx.x]) : v + red[wv][threadIdx.x];
-    if (v) {
-      if (threadIdx.x < 2) atomicMax(word, v);
-      else atomicAdd(word, v);
-    }
-  }
+  // image bases are 16-B aligned only when hw % 4 == 0
+  for_each_pixel<BND_TPB>(hw, (hw & 3) == 0, one, out, target, nullable(sel), d2_target, d2_pred);
+  unsigned long long* words = rows + (int64_t)blockIdx.y * 6 + threadIdx.x;
+  const unsigned long long m = block_reduce<2, BND_TPB>(mx, [](auto a, auto b) { return max(a, b); });
+  if (threadIdx.x < 2 && m) atomicMax(words, m);
+  const unsigned long long v = block_sum<4, BND_TPB>(cnt);
+  if (threadIdx.x < 4 && v) atomicAdd(words + 2, v);
 }
-
-constexpr int32_t BND_GRID_Y = 32768;  // images per launch (blockIdx.y is 16 bits wide)
 
 }  // namespace selunet
 
@@ -237,7 +181,7 @@ int selunet_edt_sq(const float* x, float t, int32_t n, int32_t h, int32_t w, int
                   SELUNET_EDT_MAX_SIDE, h, w);
   SELUNET_REQUIRE((int64_t)n * std::max(h, w) <= INT32_MAX, "edt_sq: n * max(h, w) must be below 2^31 (got %d x %d x %d)",
                   n, h, w);
-  SELUNET_REQUIRE(((uintptr_t)x & 3) == 0 && ((uintptr_t)d2 & 3) == 0, "edt_sq: x and d2 must be 4-B aligned");
+  SELUNET_REQUIRE(aligned(3, x, d2), "edt_sq: x and d2 must be 4-B aligned");
   const int col_blocks = (int)cdiv(w, EDT_COL_TPB);
   hipLaunchKernelGGL(edt_columns_kernel, dim3((unsigned)(n * col_blocks)), dim3(EDT_COL_TPB), 0, as_stream(stream), x,
                      t, h, w, col_blocks, d2);
@@ -260,10 +204,8 @@ int selunet_boundary_bands(const float* out, const float* sel, const float* targ
                     "boundary_bands: r2 must be strictly increasing from r2[0] >= 1 (r2[%d] = %d)", j, r2[j]);
     e.r2[j] = r2[j];
   }
-  SELUNET_REQUIRE(((uintptr_t)out & 15) == 0 && ((uintptr_t)target & 15) == 0 && ((uintptr_t)sel & 15) == 0 &&
-                      ((uintptr_t)d2_target & 15) == 0,
-                  "boundary_bands: inputs must be 16-B aligned");
-  SELUNET_REQUIRE(((uintptr_t)bins & 7) == 0, "boundary_bands: bins must be 8-B aligned");
+  SELUNET_REQUIRE(aligned(15, out, target, sel, d2_target), "boundary_bands: inputs must be 16-B aligned");
+  SELUNET_REQUIRE(aligned(7, bins), "boundary_bands: bins must be 8-B aligned");
   const int64_t p = (int64_t)n * hw;
   // p <= 2^40 over at least min(p / 1024, 2048) workgroups: a 32-bit LDS count stays below 2^30 (at the default
   // grid; SELUNET_OPT_IO_GRID can make it smaller and is for tests and small inputs only, see selunet.h)
@@ -282,18 +224,16 @@ int selunet_boundary_rows(const float* out, const float* sel, const float* targe
   SELUNET_REQUIRE(hw >= 1 && hw <= ((int64_t)1 << 24), "boundary_rows: hw must be in [1, 2^24] (got %lld)",
                   (long long)hw);
   SELUNET_REQUIRE(tol_sq >= 0, "boundary_rows: tol_sq must be >= 0 (got %d)", tol_sq);
-  const uintptr_t mask = (hw & 3) ? 3 : 15;
-  SELUNET_REQUIRE((((uintptr_t)out | (uintptr_t)target | (uintptr_t)sel | (uintptr_t)d2_target | (uintptr_t)d2_pred) &
-                   mask) == 0,
+  SELUNET_REQUIRE(aligned((hw & 3) ? 3 : 15, out, target, sel, d2_target, d2_pred),
                   "boundary_rows: inputs must be 16-B aligned (4-B when hw is not a multiple of 4)");
-  SELUNET_REQUIRE(((uintptr_t)rows & 7) == 0, "boundary_rows: rows must be 8-B aligned");
+  SELUNET_REQUIRE(aligned(7, rows), "boundary_rows: rows must be 8-B aligned");
   const unsigned gx = (unsigned)io_grid(cdiv(hw / 4, BND_TPB * 4), 64);
-  for (int32_t i0 = 0; i0 < n; i0 += BND_GRID_Y) {
+  for_image_chunks(n, IMAGE_GRID_Y, [&](int32_t i0, unsigned ny) {
     const int64_t o = (int64_t)i0 * hw;
-    hipLaunchKernelGGL(boundary_rows_kernel, dim3(gx, (unsigned)std::min(n - i0, BND_GRID_Y)), dim3(BND_TPB), 0,
-                       as_stream(stream), out + o, sel ? sel + o : nullptr, target + o, d2_target + o, d2_pred + o, hw,
-                       t_out, t_sel, tol_sq, rows + (int64_t)i0 * 6);
-  }
+    hipLaunchKernelGGL(boundary_rows_kernel, dim3(gx, ny), dim3(BND_TPB), 0, as_stream(stream), out + o,
+                       sel ? sel + o : nullptr, target + o, d2_target + o, d2_pred + o, hw, t_out, t_sel, tol_sq,
+                       rows + (int64_t)i0 * 6);
+  });
   return check_launch("boundary_rows");
 }
 

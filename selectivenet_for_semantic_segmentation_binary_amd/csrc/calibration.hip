@@ -11,6 +11,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "metrics_common.h"
 
 namespace selunet {
 
@@ -57,13 +58,12 @@ __global__ __launch_bounds__(CALIB_TPB) void calibration_bins_kernel(
     const float* score, const float* out, const float* sel, const float* __restrict__ target, int64_t p, int event,
     float t_out, float t_sel, const float* __restrict__ edges, int m, int top, double inv_temperature,
     unsigned long long* __restrict__ bins, unsigned long long* __restrict__ fine, unsigned long long* __restrict__ misc) {
-  // NaN padding: `s >= NaN` is false, so the padded list keeps its true-prefix shape for s = +inf too
   __shared__ float thr[CALIB_EDGES];
   __shared__ unsigned long long lbins[CALIB_EDGES * CALIB_COLS];
   __shared__ unsigned lfine[CALIB_FINE_WORDS];
   __shared__ unsigned lmisc[2];
   const int cells = (m + 1) * CALIB_COLS;
-  for (int i = threadIdx.x; i < CALIB_EDGES; i += CALIB_TPB) thr[i] = i < m ? edges[i] : __builtin_nanf("");
+  stage_thresholds<CALIB_TPB>(thr, edges, m);
   for (int i = threadIdx.x; i < cells; i += CALIB_TPB) lbins[i] = 0;
   if (fine)
     for (int i = threadIdx.x; i < CALIB_FINE_WORDS; i += CALIB_TPB) lfine[i] = 0;
@@ -92,8 +92,9 @@ __global__ __launch_bounds__(CALIB_TPB) void calibration_bins_kernel(
     f_ev[0] = f_ev[1] = 0;
   };
   auto one = [&](float sc, float o, float s, float t) {
-    const int lab = (int)(uint8_t)t;  // as seg_metrics_kernel
-    if (!(sel == nullptr || s >= t_sel)) return;
+    // pixel_state's 5, 4 and cm cells in turn, from its own three expressions (a NaN score is in no cell)
+    if (!pixel_selected(s, sel != nullptr, t_sel)) return;
+    const int lab = pixel_label(t);
     if (lab >= 2) {
       other_labels += 1;
       return;
@@ -102,9 +103,8 @@ __global__ __launch_bounds__(CALIB_TPB) void calibration_bins_kernel(
       nan_scores += 1;
       return;
     }
-    const int e = event == 0 ? lab : (int)((o >= t_out) == (lab == 1));
-    int b = 0;  // the true-prefix length over thr[0 .. 2 * top - 2]
-    for (int st = top; st > 0; st >>= 1) b += sc >= thr[b + st - 1] ? st : 0;
+    const int e = event == 0 ? lab : (int)(pixel_pred(o, t_out) == lab);
+    const int b = true_prefix(thr, sc, top);
     if (b != cur_bin) {
       flush_bin();
       cur_bin = b;
@@ -124,32 +124,14 @@ __global__ __launch_bounds__(CALIB_TPB) void calibration_bins_kernel(
     }
   };
 
-  const int64_t p4 = p >> 2;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const f32x4 zero = {0, 0, 0, 0};
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < p4; i += stride) {
-    const f32x4 sc = *reinterpret_cast<const f32x4*>(score + i * 4);
-    const f32x4 t = *reinterpret_cast<const f32x4*>(target + i * 4);
-    const f32x4 o = event ? *reinterpret_cast<const f32x4*>(out + i * 4) : zero;
-    const f32x4 s = sel ? *reinterpret_cast<const f32x4*>(sel + i * 4) : zero;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) one(sc[j], o[j], s[j], t[j]);
-  }
-  for (int64_t i = p4 * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < p; i += stride)
-    one(score[i], event ? out[i] : 0.0f, sel ? sel[i] : 0.0f, target[i]);
+  // score may be the same plane as out or sel: for_each_pixel's planes are not __restrict__
+  for_each_pixel<CALIB_TPB>(p, true, one, score, nullable(event ? out : nullptr), nullable(sel), target);
   flush_bin();
   flush_cell();
-  {
-    unsigned a = nan_scores, b = other_labels;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      a += __shfl_xor(a, o, 64);
-      b += __shfl_xor(b, o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-      if (a) atomicAdd(&lmisc[0], a);
-      if (b) atomicAdd(&lmisc[1], b);
-    }
+  const unsigned a = wave_sum(nan_scores), b = wave_sum(other_labels);
+  if ((threadIdx.x & 63) == 0) {
+    if (a) atomicAdd(&lmisc[0], a);
+    if (b) atomicAdd(&lmisc[1], b);
   }
   __syncthreads();
   // One thread per word, so that a wave's atomic covers 512 contiguous bytes (as the sweep's closing block)
@@ -180,14 +162,11 @@ int selunet_calibration_bins(const float* score, const float* out, const float* 
                   SELUNET_CALIB_MAX_EDGES, m);
   SELUNET_REQUIRE(std::isfinite(inv_temperature) && inv_temperature > 0,
                   "calibration_bins: inv_temperature must be finite and > 0 (got %g)", inv_temperature);
-  SELUNET_REQUIRE(((uintptr_t)score & 15) == 0 && ((uintptr_t)target & 15) == 0 && ((uintptr_t)sel & 15) == 0 &&
-                      (event == 0 || ((uintptr_t)out & 15) == 0),
+  SELUNET_REQUIRE(aligned(15, score, target, sel) && (event == 0 || aligned(15, out)),
                   "calibration_bins: score, out, sel and target must be 16-B aligned");
-  SELUNET_REQUIRE(((uintptr_t)edges & 3) == 0, "calibration_bins: edges must be 4-B aligned");
-  SELUNET_REQUIRE(((uintptr_t)bins & 7) == 0 && ((uintptr_t)fine & 7) == 0 && ((uintptr_t)misc & 7) == 0,
-                  "calibration_bins: bins, fine and misc must be 8-B aligned");
-  int top = 1;
-  while (top * 2 <= m) top *= 2;
+  SELUNET_REQUIRE(aligned(3, edges), "calibration_bins: edges must be 4-B aligned");
+  SELUNET_REQUIRE(aligned(7, bins, fine, misc), "calibration_bins: bins, fine and misc must be 8-B aligned");
+  const int top = search_top(m);
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(p / 4 + 1, CALIB_TPB), CALIB_GRID));
   hipLaunchKernelGGL(calibration_bins_kernel, dim3(grid), dim3(CALIB_TPB), 0, as_stream(stream), score, out, sel,
                      target, p, (int)event, t_out, t_sel, edges, (int)m, top, inv_temperature, bins, fine, misc);

@@ -42,6 +42,9 @@ int x2_tile_queue_prepare();
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// every pointer (a null one too) is a multiple of mask + 1 = 4, 8 or 16 bytes
+template <typename... P> inline bool aligned(uintptr_t mask, const P*... p) { return ((... | (uintptr_t)p) & mask) == 0; }
+
 // Workgroups of a grid-stride I/O, metrics or prediction launch: the launcher's own rule `want` under its own cap,
 // or under SELUNET_OPT_IO_GRID where that is set (every such kernel strides by its gridDim, so any grid >= 1 does
 // the same work; the option is for tests and small inputs: 32-bit partial counts are sized for the default grids)
@@ -84,6 +87,35 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+__device__ __forceinline__ unsigned wave_sum(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// The workgroup's reduction (op: sum or max, of either width) of K 32-bit partial values per thread: per wave
+// by shuffles, per workgroup through LDS. Thread k < K returns the 64-bit result of word k, the others 0; the
+// caller closes with its own integer atomic per word. Every thread of the TPB calls it, once per kernel for
+// one K and op (the LDS words are the instantiation's own).
+template <int K, int TPB, typename Op>
+__device__ __forceinline__ unsigned long long block_reduce(const unsigned (&c)[K], Op op) {
+  __shared__ unsigned red[TPB / 64][K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    unsigned v = c[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = op(v, (unsigned)__shfl_xor(v, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
+  }
+  __syncthreads();
+  unsigned long long s = 0;
+  if (threadIdx.x < K)
+    for (int wv = 0; wv < TPB / 64; ++wv) s = op(s, (unsigned long long)red[wv][threadIdx.x]);
+  return s;
+}
+template <int K, int TPB> __device__ __forceinline__ unsigned long long block_sum(const unsigned (&c)[K]) {
+  return block_reduce<K, TPB>(c, [](auto a, auto b) { return a + b; });
 }
 
 // *amax = max(*amax, wave max of v >= 0) as one atomic per wave on the float bits (non-negative

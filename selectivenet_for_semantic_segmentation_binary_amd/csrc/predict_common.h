@@ -34,7 +34,8 @@ __device__ __forceinline__ uint32_t prob_level(float v) {
 }
 
 // A pixel's class {0 background, 1 tumor, 2 abstained}: `not (sel >= t_sel)` abstains, so a NaN selection
-// abstains; a NaN output is background (seg_metrics_kernel's rule).
+// abstains; a NaN output is background. The two comparisons are pixel_state's (metrics_common.h), the rule of
+// the eval metrics, without a label: they must stay the same expressions.
 __device__ __forceinline__ int pixel_class(bool selective, float s, float o, float t_sel, float t_out) {
   return (selective && !(s >= t_sel)) ? 2 : (o >= t_out ? 1 : 0);
 }
@@ -43,26 +44,11 @@ __device__ __forceinline__ int pixel_class(bool selective, float s, float o, flo
 __device__ __forceinline__ uint32_t mask_level(int cls) { return cls == 2 ? 127u : (cls == 1 ? 255u : 0u); }
 
 // counts += {c[0], c[1], c[2], c[0] + c[1] + c[2]} summed over the workgroup (PRED_TPB threads, all of them
-// calling): per wave by shuffles, per workgroup through LDS, then four integer atomics.
+// calling) by block_sum (common.h), then four integer atomics. Word 3, `pixels`, is the three classes' sum.
 __device__ __forceinline__ void add_class_counts(const unsigned (&c)[3], unsigned long long* __restrict__ counts) {
-  __shared__ unsigned red[PRED_TPB / 64][3];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    unsigned v = c[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    // words 0..2: the class of this thread; word 3, `pixels`: all three
-    unsigned long long s = 0;
-    for (int wv = 0; wv < PRED_TPB / 64; ++wv)
-      for (int k = 0; k < 3; ++k)
-        if (threadIdx.x == 3 || threadIdx.x == k) s += red[wv][k];
-    if (s) atomicAdd(counts + threadIdx.x, s);
-  }
+  const unsigned c4[4] = {c[0], c[1], c[2], c[0] + c[1] + c[2]};
+  const unsigned long long s = block_sum<4, PRED_TPB>(c4);
+  if (threadIdx.x < 4 && s) atomicAdd(counts + threadIdx.x, s);
 }
 
 // The argument rules the per-tile calls share; `fn` names the call in the message.

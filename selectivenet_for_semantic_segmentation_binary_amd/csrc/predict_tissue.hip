@@ -65,7 +65,6 @@ __global__ __launch_bounds__(PRED_TPB) void tile_tissue_counts_kernel(const uint
                                                                       int h, int w, const int32_t* __restrict__ origins,
                                                                       int th, int tw, int flip,
                                                                       int32_t* __restrict__ counts) {
-  __shared__ unsigned red[PRED_TPB / 64];
   const bool fy = flip & 2, fx = flip & 1;
   const int t = blockIdx.x;
   const int64_t y0 = origins[2 * t], x0 = origins[2 * t + 1];
@@ -73,7 +72,7 @@ __global__ __launch_bounds__(PRED_TPB) void tile_tissue_counts_kernel(const uint
   const int rows = (th + (int)gridDim.y - 1) / (int)gridDim.y;
   const int y_lo = std::min(th, (int)blockIdx.y * rows), y_hi = std::min(th, y_lo + rows);
   const int total = (y_hi - y_lo) * wq;  // th * tw < 2^31
-  unsigned c = 0;
+  unsigned c[1] = {0};
   for (int i = threadIdx.x; i < total; i += PRED_TPB) {
     const int y = y_lo + i / wq, xq = i % wq;
     const int ys = reflect_index(y0 + y, h);
@@ -83,24 +82,17 @@ __global__ __launch_bounds__(PRED_TPB) void tile_tissue_counts_kernel(const uint
       uint32_t v;
       __builtin_memcpy(&v, row + (fx ? w - 4 - xs0 : xs0), 4);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) c += ((v >> (8 * j)) & 255u) != 0u;
+      for (int j = 0; j < 4; ++j) c[0] += ((v >> (8 * j)) & 255u) != 0u;
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int xs = reflect_index(xs0 + j, w);
-        c += row[fx ? w - 1 - xs : xs] != 0;
+        c[0] += row[fx ? w - 1 - xs : xs] != 0;
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned s = 0;
-    for (int wv = 0; wv < PRED_TPB / 64; ++wv) s += red[wv];
-    if (s) atomicAdd(counts + t, (int32_t)s);
-  }
+  const unsigned long long s = block_sum<1, PRED_TPB>(c);  // < 2^31: th * tw
+  if (threadIdx.x == 0 && s) atomicAdd(counts + t, (int32_t)s);
 }
 
 // One thread per 4 pixels of a row, an aligned 4-B load of either plane where its row's address allows it
@@ -152,7 +144,7 @@ int selunet_tissue_plane(const uint8_t* img, int32_t h, int32_t w, int32_t brigh
   SELUNET_REQUIRE(pitch >= w && pitch % 4 == 0,
                   "tissue_plane: the plane's row pitch must hold the width and be a multiple of 4 (got %d for %d)", pitch,
                   w);
-  SELUNET_REQUIRE(((uintptr_t)plane & 3) == 0, "tissue_plane: plane must be 4-B aligned");
+  SELUNET_REQUIRE(aligned(3, plane), "tissue_plane: plane must be 4-B aligned");
   const int64_t total = (int64_t)h * (pitch / 4);
   const int64_t blocks = io_grid(cdiv(total, PRED_TPB), 8192);
   hipLaunchKernelGGL(tissue_plane_kernel, dim3((unsigned)blocks), dim3(PRED_TPB), 0, as_stream(stream), img, h, w,
@@ -170,7 +162,7 @@ int selunet_tile_tissue_counts(const uint8_t* plane, int64_t pitch, int32_t h, i
                   "tile_tissue_counts: flip must be in [0, 3]: bit 1 rows, bit 0 columns (got %d)", flip);
   SELUNET_REQUIRE((int64_t)th * tw < ((int64_t)1 << 31),
                   "tile_tissue_counts: a window of %d x %d positions does not fit a 32-bit count", th, tw);
-  SELUNET_REQUIRE(((uintptr_t)counts & 3) == 0, "tile_tissue_counts: counts must be 4-B aligned");
+  SELUNET_REQUIRE(aligned(3, counts), "tile_tissue_counts: counts must be 4-B aligned");
   const unsigned slabs = (unsigned)std::min<int64_t>(cdiv(th, TISSUE_SLAB_ROWS), 1024);
   hipLaunchKernelGGL(tile_tissue_counts_kernel, dim3((unsigned)n, slabs), dim3(PRED_TPB), 0, as_stream(stream), plane,
                      pitch, h, w, origins, th, tw, flip, counts);
@@ -185,7 +177,7 @@ int selunet_tissue_class_counts(const uint8_t* mask, int64_t mask_pitch, const u
   SELUNET_REQUIRE(mask_pitch >= w && pitch >= w,
                   "tissue_class_counts: the row pitches of mask and plane must hold the width %d (got %lld, %lld)", w,
                   (long long)mask_pitch, (long long)pitch);
-  SELUNET_REQUIRE(((uintptr_t)counts & 7) == 0, "tissue_class_counts: counts must be 8-B aligned");
+  SELUNET_REQUIRE(aligned(7, counts), "tissue_class_counts: counts must be 8-B aligned");
   // the per-thread and per-wave partial counts are 32 bits wide; H W < 2^32 by the bound above
   const int64_t total = (int64_t)h * ((w + 3) / 4);
   const int64_t blocks = io_grid(cdiv(total, PRED_TPB), 2048);

@@ -265,8 +265,6 @@ __global__ __launch_bounds__(PRED_TPB) void tta_finalize_kernel(
   add_class_counts(c, counts);
 }
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace selunet
 
 using namespace selunet;
@@ -280,7 +278,7 @@ int selunet_tile_gather_flip(const uint8_t* img, int32_t h, int32_t w, const int
   SELUNET_REQUIRE(mode >= 0 && mode <= 2, "tile_gather_flip: mode 0 'RGB', 1 'GH', 2 'H_RGB' (got %d)", mode);
   SELUNET_REQUIRE(flip >= 0 && flip <= 3, "tile_gather_flip: flip must be in [0, 3]: bit 1 rows, bit 0 columns (got %d)",
                   flip);
-  SELUNET_REQUIRE(aligned16(x), "tile_gather_flip: x must be 16-B aligned");
+  SELUNET_REQUIRE(aligned(15, x), "tile_gather_flip: x must be 16-B aligned");
   const int64_t total = (int64_t)n * th * (tw / 4);
   const dim3 grid((unsigned)io_grid(cdiv(total, PRED_TPB), 8192));
   auto kernel = mode == 0 ? tile_gather_flip_kernel<3, false> : mode == 1 ? tile_gather_flip_kernel<2, false>
@@ -316,8 +314,8 @@ int selunet_tta_accumulate(const float* out, const float* sel, const int32_t* or
   SELUNET_REQUIRE(ws >= w && ws % 8 == 0,
                   "tta_accumulate: the sums' row stride must hold the image and be a multiple of 8 (got %d for width %d)",
                   ws, w);
-  SELUNET_REQUIRE(aligned16(out) && aligned16(sel) && aligned16(sum_out) && aligned16(sum_sel) && aligned16(votes) &&
-                      aligned16(sel_votes), "tta_accumulate: tiles and planes must be 16-B aligned");
+  SELUNET_REQUIRE(aligned(15, out, sel, sum_out, sum_sel, votes, sel_votes),
+                  "tta_accumulate: tiles and planes must be 16-B aligned");
   const int64_t total = (int64_t)n * (th - 2 * halo) * ((tw - 2 * halo) / 8 + 1);
   const int64_t blocks = io_grid(cdiv(total, PRED_TPB), 8192);
   hipLaunchKernelGGL(tta_accumulate_kernel, dim3((unsigned)blocks), dim3(PRED_TPB), 0, as_stream(stream), out, sel,
@@ -351,11 +349,9 @@ int selunet_tta_finalize(const float* a_out, const float* a_sel, const uint8_t* 
   SELUNET_REQUIRE(members == 4 || (hb >= h && hb % 8 == 0),
                   "tta_finalize: the transposed row stride hb must hold the height and be a multiple of 8 (got %d for %d)",
                   hb, h);
-  SELUNET_REQUIRE(aligned16(a_out) && aligned16(a_sel) && aligned16(a_votes) && aligned16(a_sel_votes) &&
-                      aligned16(b_out) && aligned16(b_sel) && aligned16(b_votes) && aligned16(b_sel_votes) &&
-                      aligned16(logit_plane) && aligned16(sel_plane) && aligned16(mask) && aligned16(prob8) &&
-                      aligned16(votes) && aligned16(sel_votes), "tta_finalize: planes must be 16-B aligned");
-  SELUNET_REQUIRE(((uintptr_t)counts & 7) == 0, "tta_finalize: counts must be 8-B aligned");
+  SELUNET_REQUIRE(aligned(15, a_out, a_sel, a_votes, a_sel_votes, b_out, b_sel, b_votes, b_sel_votes, logit_plane,
+                          sel_plane, mask, prob8, votes, sel_votes), "tta_finalize: planes must be 16-B aligned");
+  SELUNET_REQUIRE(aligned(7, counts), "tta_finalize: counts must be 8-B aligned");
   const dim3 grid((unsigned)cdiv(wa, FIN_TILE), (unsigned)cdiv(h, FIN_TILE));
   hipLaunchKernelGGL(tta_finalize_kernel, grid, dim3(PRED_TPB), 0, as_stream(stream), a_out, a_sel, a_votes,
                      a_sel_votes, b_out, b_sel, b_votes, b_sel_votes, members, h, w, wa, hb, t_out, t_sel, logit_plane,

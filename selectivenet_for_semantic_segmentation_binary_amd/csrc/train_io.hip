@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "metrics_common.h"
 #include "prep_pixel.h"
 
 namespace selunet {
@@ -69,47 +70,20 @@ __global__ void prep_batch_kernel(const uint8_t* __restrict__ img, const uint8_t
 
 // counts[0..3] = confusion matrix cm[label][pred] over the counted pixels (row-major, as
 // Evaluator.confusion_matrix), counts[4] = selected pixels, counts[5] = all pixels (label.size).
-// A pixel is counted iff 0 <= label < 2 and (no selection head or sel >= t_sel).
-// pred = out >= t_out: t_out / t_sel are the smallest fp32 logits the reference's host rule maps
-// to 1 (computed once on the host from the same numpy expression, see metrics.py).
+// A pixel is counted iff 0 <= label < 2 and selected: pixel_state's rule (metrics_common.h).
 // The workgroups blockIdx.x of gridDim.x share the p pixels; a grid's y dimension is the caller's.
 __device__ __forceinline__ void seg_metrics_block(const float* __restrict__ out, const float* __restrict__ sel,
                                                   const float* __restrict__ target, int64_t p, float t_out,
                                                   float t_sel, unsigned long long* __restrict__ counts) {
   unsigned c[5] = {0, 0, 0, 0, 0};
-  const int64_t p4 = p >> 2;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  auto one = [&](float o, float s, float t) {
-    // label.astype('uint8') of a {0,1} float target (train.py:206; eval.py:229)
-    const int lab = (int)(uint8_t)t;
-    const bool selected = sel == nullptr || s >= t_sel;
-    c[4] += selected;
-    if (selected && lab < 2) c[lab * 2 + (o >= t_out ? 1 : 0)] += 1;
+  auto one = [&](float o, float t, float s) {
+    const int st = pixel_state(o, s, t, sel != nullptr, t_out, t_sel);
+    c[4] += st != 5;
+    if (st < 4) c[st] += 1;
   };
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < p4; i += stride) {
-    const f32x4 o = *reinterpret_cast<const f32x4*>(out + i * 4);
-    const f32x4 t = *reinterpret_cast<const f32x4*>(target + i * 4);
-    const f32x4 s = sel ? *reinterpret_cast<const f32x4*>(sel + i * 4) : f32x4{0, 0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) one(o[j], s[j], t[j]);
-  }
-  for (int64_t i = p4 * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < p; i += stride)
-    one(out[i], sel ? sel[i] : 0.0f, target[i]);
-  __shared__ unsigned red[IO_TPB / 64][5];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    unsigned v = c[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    unsigned long long s = 0;
-    for (int wv = 0; wv < IO_TPB / 64; ++wv) s += red[wv][threadIdx.x];
-    atomicAdd(counts + threadIdx.x, s);
-  }
+  for_each_pixel<IO_TPB>(p, true, one, out, target, nullable(sel));
+  const unsigned long long s = block_sum<5, IO_TPB>(c);
+  if (threadIdx.x < 5) atomicAdd(counts + threadIdx.x, s);
   if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(counts + 5, (unsigned long long)p);
 }
 
@@ -151,7 +125,6 @@ __global__ void seg_metrics_rows_kernel(const float* __restrict__ out, const flo
 // 1024 threads: the searches are chains of dependent LDS reads, and sixteen waves per CU hide their
 // latency where four did not (16 x 256 x 256 pixels: 168 us with 256 threads).
 constexpr int64_t PATCH_MAX_HW = (int64_t)1 << 20;  // pixels per image the per-image calls take
-constexpr int32_t PATCH_GRID_Y = 32768;             // images per launch (blockIdx.y)
 constexpr int AUC_CHUNK = SELUNET_AUC_CHUNK;
 constexpr int AUC_TPB = 1024;
 constexpr unsigned AUC_SENTINEL = 0xFFFFFFFFu;
@@ -169,16 +142,16 @@ __global__ __launch_bounds__(AUC_TPB) void patch_auc_kernel(const float* __restr
                                                             const float* __restrict__ target, int64_t hw,
                                                             float t_sel, unsigned long long* __restrict__ rows) {
   __shared__ unsigned keys[AUC_CHUNK];
-  __shared__ unsigned red[AUC_TPB / 64][4];
   const int64_t base = (int64_t)blockIdx.y * hw;
   out += base;
   target += base;
   if (sel) sel += base;
   const int tid = threadIdx.x;
-  // label.astype('uint8') < 2 and selected, as seg_metrics_kernel; NaN logits are told apart by the caller
+  // the label of a counted pixel (pixel_state's cm cells, whatever the prediction), else 2; NaN logits are told
+  // apart by the caller
   auto label_of = [&](float s, float t) {
-    const int lab = (int)(uint8_t)t;
-    return (sel == nullptr || s >= t_sel) && lab < 2 ? lab : 2;
+    const int lab = pixel_label(t);
+    return pixel_selected(s, sel != nullptr, t_sel) && lab < 2 ? lab : 2;
   };
 
   // ---- this chunk's considered negatives as keys, everything else (and the ragged tail) the sentinel
@@ -299,22 +272,10 @@ __global__ __launch_bounds__(AUC_TPB) void patch_auc_kernel(const float* __restr
     }
   }
 
-  // ---- per wave by shuffles, then one 64-bit integer atomic per word and workgroup
-  const int lane = tid & 63, wave = tid >> 6;
-  unsigned part[4] = {two_u, n_pos, n_neg, n_nan};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    unsigned v = part[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (tid < 4) {
-    unsigned long long sum = 0;
-    for (int wv = 0; wv < AUC_TPB / 64; ++wv) sum += red[wv][tid];
-    if (sum) atomicAdd(rows + blockIdx.y * 4 + tid, sum);
-  }
+  // ---- one 64-bit integer atomic per word and workgroup
+  const unsigned part[4] = {two_u, n_pos, n_neg, n_nan};
+  const unsigned long long sum = block_sum<4, AUC_TPB>(part);
+  if (tid < 4 && sum) atomicAdd(rows + blockIdx.y * 4 + tid, sum);
 }
 
 // Risk-coverage sweep: seg_metrics_kernel's counts at k selection thresholds in one pass. With the
@@ -340,12 +301,11 @@ constexpr int64_t SWEEP_MAX_PIXELS = (int64_t)1 << 40;
 __global__ __launch_bounds__(IO_TPB) void seg_metrics_sweep_kernel(
     const float* __restrict__ out, const float* __restrict__ sel, const float* __restrict__ target, int64_t p,
     float t_out, const float* __restrict__ t_sel, int k, int top, unsigned long long* __restrict__ bins) {
-  // NaN padding: `s >= NaN` is false, so the padded list keeps its true-prefix shape for s = +inf too
   __shared__ float thr[SELUNET_SWEEP_MAX];
   __shared__ unsigned hist[SWEEP_WAVES][(SELUNET_SWEEP_MAX + 1) * SWEEP_CLASSES];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int cells = (k + 1) * SWEEP_CLASSES;
-  for (int i = threadIdx.x; i < SELUNET_SWEEP_MAX; i += IO_TPB) thr[i] = i < k ? t_sel[i] : __builtin_nanf("");
+  stage_thresholds<IO_TPB>(thr, t_sel, k);
   for (int i = threadIdx.x; i < cells; i += IO_TPB)
 #pragma unroll
     for (int wv = 0; wv < SWEEP_WAVES; ++wv) hist[wv][i] = 0;
@@ -354,15 +314,9 @@ __global__ __launch_bounds__(IO_TPB) void seg_metrics_sweep_kernel(
 
   // the true-prefix length over thr[0 .. 2*top-2] by binary search, then the last entry on its own
   // (k = 256 has 257 bins, one more than 8 halvings tell apart)
-  auto bin_of = [&](float s) {
-    int b = 0;
-    for (int st = top; st > 0; st >>= 1) b += s >= thr[b + st - 1] ? st : 0;
-    return b + (s >= thr[SELUNET_SWEEP_MAX - 1] ? 1 : 0);
-  };
-  auto class_of = [&](float o, float t) {
-    const int lab = (int)(uint8_t)t;  // as seg_metrics_kernel
-    return lab < 2 ? lab * 2 + (o >= t_out ? 1 : 0) : 4;
-  };
+  auto bin_of = [&](float s) { return true_prefix(thr, s, top) + (s >= thr[SELUNET_SWEEP_MAX - 1] ? 1 : 0); };
+  // pixel_state without a selection plane: the cm cell, or 4 for a label >= 2
+  auto class_of = [&](float o, float t) { return pixel_state(o, 0.0f, t, false, t_out, 0.0f); };
   auto count = [&](int b, int cls) {
     const unsigned long long active = __ballot(1);
     const int b0 = __builtin_amdgcn_readfirstlane(b);
@@ -421,7 +375,7 @@ int selunet_prep_batch_mode(const uint8_t* img, const uint8_t* lab, const uint8_
   SELUNET_REQUIRE(mode >= 0 && mode <= 2, "prep_batch_mode: mode 0 'RGB', 1 'GH', 2 'H_RGB' (got %d)", mode);
   if (mode != 2) return selunet_prep_batch(img, lab, flips, n, h, w, mode == 0 ? 3 : 2, x, target, stream);
   SELUNET_REQUIRE(img && lab && x && target && n > 0 && h > 0 && w > 0 && w % 4 == 0, "prep_batch: bad arguments");
-  SELUNET_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)target & 15) == 0, "prep_batch: outputs must be 16-B aligned");
+  SELUNET_REQUIRE(aligned(15, x, target), "prep_batch: outputs must be 16-B aligned");
   const int64_t total = (int64_t)n * h * (w / 4);
   const unsigned grid = (unsigned)io_grid(cdiv(total, IO_TPB), 8192);
   hipLaunchKernelGGL((prep_batch_kernel<3, true>), dim3(grid), dim3(IO_TPB), 0, as_stream(stream), img, lab, flips, n, h,
@@ -434,7 +388,7 @@ int selunet_prep_batch(const uint8_t* img, const uint8_t* lab, const uint8_t* fl
   SELUNET_REQUIRE(img && lab && x && target && n > 0 && h > 0 && w > 0, "prep_batch: bad arguments");
   SELUNET_REQUIRE(cin == 3 || cin == 2, "prep_batch: cin 3 (input_type 'RGB') or 2 ('GH', utils/data_utils.py:223-224)");
   SELUNET_REQUIRE(w % 4 == 0, "prep_batch: width must be a multiple of 4");
-  SELUNET_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)target & 15) == 0, "prep_batch: outputs must be 16-B aligned");
+  SELUNET_REQUIRE(aligned(15, x, target), "prep_batch: outputs must be 16-B aligned");
   const int64_t total = (int64_t)n * h * (w / 4);
   const unsigned grid = (unsigned)io_grid(cdiv(total, IO_TPB), 8192);
   hipLaunchKernelGGL(cin == 3 ? prep_batch_kernel<3> : prep_batch_kernel<2>, dim3(grid), dim3(IO_TPB), 0,
@@ -445,8 +399,7 @@ int selunet_prep_batch(const uint8_t* img, const uint8_t* lab, const uint8_t* fl
 int selunet_seg_metrics(const float* out, const float* sel, const float* target, int64_t p, float t_out, float t_sel,
                         unsigned long long* counts, void* stream) {
   SELUNET_REQUIRE(out && target && counts && p > 0, "seg_metrics: bad arguments");
-  SELUNET_REQUIRE(((uintptr_t)out & 15) == 0 && ((uintptr_t)target & 15) == 0 && ((uintptr_t)sel & 15) == 0,
-                  "seg_metrics: inputs must be 16-B aligned");
+  SELUNET_REQUIRE(aligned(15, out, target, sel), "seg_metrics: inputs must be 16-B aligned");
   const unsigned grid = (unsigned)io_grid(cdiv(p / 4 + 1, IO_TPB), 2048);
   hipLaunchKernelGGL(seg_metrics_kernel, dim3(grid), dim3(IO_TPB), 0, as_stream(stream), out, sel, target, p, t_out,
                      t_sel, counts);
@@ -460,9 +413,8 @@ static int patch_rows_args(const char* fn, const float* out, const float* sel, c
   SELUNET_REQUIRE(n >= 1, "%s: n must be >= 1 (got %d)", fn, n);
   SELUNET_REQUIRE(hw >= 1 && hw % 4 == 0 && hw <= PATCH_MAX_HW,
                   "%s: hw must be a multiple of 4 in [4, 2^20] (got %lld)", fn, (long long)hw);
-  SELUNET_REQUIRE(((uintptr_t)out & 15) == 0 && ((uintptr_t)target & 15) == 0 && ((uintptr_t)sel & 15) == 0,
-                  "%s: inputs must be 16-B aligned", fn);
-  SELUNET_REQUIRE(((uintptr_t)rows & 7) == 0, "%s: rows must be 8-B aligned", fn);
+  SELUNET_REQUIRE(aligned(15, out, target, sel), "%s: inputs must be 16-B aligned", fn);
+  SELUNET_REQUIRE(aligned(7, rows), "%s: rows must be 8-B aligned", fn);
   return SELUNET_OK;
 }
 
@@ -471,12 +423,11 @@ int selunet_seg_metrics_rows(const float* out, const float* sel, const float* ta
   if (int rc = patch_rows_args("seg_metrics_rows", out, sel, target, n, hw, rows)) return rc;
   // at least four 16-B loads per thread before a workgroup's five closing atomics
   const unsigned gx = (unsigned)io_grid(cdiv(hw / 4, IO_TPB * 4), 64);
-  for (int32_t i0 = 0; i0 < n; i0 += PATCH_GRID_Y) {  // a grid's y dimension is 16 bits wide
+  for_image_chunks(n, IMAGE_GRID_Y, [&](int32_t i0, unsigned ny) {
     const int64_t o = (int64_t)i0 * hw;
-    hipLaunchKernelGGL(seg_metrics_rows_kernel, dim3(gx, (unsigned)std::min(n - i0, PATCH_GRID_Y)), dim3(IO_TPB), 0,
-                       as_stream(stream), out + o, sel ? sel + o : nullptr, target + o, hw, t_out, t_sel,
-                       rows + (int64_t)i0 * 6);
-  }
+    hipLaunchKernelGGL(seg_metrics_rows_kernel, dim3(gx, ny), dim3(IO_TPB), 0, as_stream(stream), out + o,
+                       sel ? sel + o : nullptr, target + o, hw, t_out, t_sel, rows + (int64_t)i0 * 6);
+  });
   return check_launch("seg_metrics_rows");
 }
 
@@ -485,13 +436,12 @@ int selunet_patch_auc(const float* out, const float* sel, const float* target, i
   if (int rc = patch_rows_args("patch_auc", out, sel, target, n, hw, rows)) return rc;
   const unsigned gx = (unsigned)cdiv(hw, (int64_t)AUC_CHUNK);
   // images per launch: blockIdx.y's 16 bits, and at most 2^31 threads in a grid
-  const int32_t per = (int32_t)std::min<int64_t>(PATCH_GRID_Y, ((int64_t)1 << 31) / ((int64_t)gx * AUC_TPB));
-  for (int32_t i0 = 0; i0 < n; i0 += per) {
+  const int32_t per = (int32_t)std::min<int64_t>(IMAGE_GRID_Y, ((int64_t)1 << 31) / ((int64_t)gx * AUC_TPB));
+  for_image_chunks(n, per, [&](int32_t i0, unsigned ny) {
     const int64_t o = (int64_t)i0 * hw;
-    hipLaunchKernelGGL(patch_auc_kernel, dim3(gx, (unsigned)std::min(n - i0, per)), dim3(AUC_TPB), 0,
-                       as_stream(stream), out + o, sel ? sel + o : nullptr, target + o, hw, t_sel,
-                       rows + (int64_t)i0 * 4);
-  }
+    hipLaunchKernelGGL(patch_auc_kernel, dim3(gx, ny), dim3(AUC_TPB), 0, as_stream(stream), out + o,
+                       sel ? sel + o : nullptr, target + o, hw, t_sel, rows + (int64_t)i0 * 4);
+  });
   return check_launch("patch_auc");
 }
 
@@ -501,12 +451,9 @@ int selunet_seg_metrics_sweep(const float* out, const float* sel, const float* t
   SELUNET_REQUIRE(p > 0 && p <= SWEEP_MAX_PIXELS, "seg_metrics_sweep: p must be in [1, 2^40] (got %lld)", (long long)p);
   SELUNET_REQUIRE(k >= 1 && k <= SELUNET_SWEEP_MAX, "seg_metrics_sweep: k must be in [1, %d] (got %d)",
                   SELUNET_SWEEP_MAX, k);
-  SELUNET_REQUIRE(((uintptr_t)out & 15) == 0 && ((uintptr_t)target & 15) == 0 && ((uintptr_t)sel & 15) == 0,
-                  "seg_metrics_sweep: inputs must be 16-B aligned");
-  SELUNET_REQUIRE(((uintptr_t)t_sel & 3) == 0 && ((uintptr_t)bins & 7) == 0,
-                  "seg_metrics_sweep: t_sel must be 4-B and bins 8-B aligned");
-  int top = 1;
-  while (top * 2 <= std::min(k, SELUNET_SWEEP_MAX - 1)) top *= 2;
+  SELUNET_REQUIRE(aligned(15, out, target, sel), "seg_metrics_sweep: inputs must be 16-B aligned");
+  SELUNET_REQUIRE(aligned(3, t_sel) && aligned(7, bins), "seg_metrics_sweep: t_sel must be 4-B and bins 8-B aligned");
+  const int top = search_top(std::min(k, SELUNET_SWEEP_MAX - 1));
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(p / 4 + 1, IO_TPB), SWEEP_GRID));
   hipLaunchKernelGGL(seg_metrics_sweep_kernel, dim3(grid), dim3(IO_TPB), 0, as_stream(stream), out, sel, target, p,
                      t_out, t_sel, k, top, bins);

@@ -268,8 +268,7 @@ def evaluate(args):
     print(f'    mIoU:{res["mIoU"]}')
     print(f'    IoU_class:{iou_class}')
     os.makedirs(args.save_dir, exist_ok=True)
-    with open(os.path.join(args.save_dir, "performance.json"), "w") as fh:
-        json.dump(res, fh, indent=1)
+    _write_json(args.save_dir, "performance.json", res)
     if sweep is not None:
         res = dict(res, risk_coverage=report_sweep(sweep.curve(), args.target_coverage, args.save_dir))
     if report is not None:
@@ -287,6 +286,19 @@ def _cell(v):
     return repr(v) if isinstance(v, float) else str(v)
 
 
+def _write_csv(save_dir, name, columns, rows):
+    """The header line, then one line per row (a sequence of cell values)."""
+    with open(os.path.join(save_dir, name), "w") as fh:
+        fh.write(",".join(columns) + "\n")
+        for r in rows:
+            fh.write(",".join(_cell(v) for v in r) + "\n")
+
+
+def _write_json(save_dir, name, doc):
+    with open(os.path.join(save_dir, name), "w") as fh:
+        json.dump(doc, fh, indent=1)
+
+
 def report_calibration(doc, save_dir):
     """Print one line per view of `metrics.CalibrationReport.report()` and write calibration.json (the whole
     document) and calibration_bins.csv (one row per view and reliability bin)."""
@@ -301,13 +313,9 @@ def report_calibration(doc, save_dir):
             f'{x:10.6f}' for x in (s["ece"], s["top_label_ece"], s["mce"], s["brier"], s["nll"], f["temperature"],
                                    f["nll_fitted"])))
     os.makedirs(save_dir, exist_ok=True)
-    with open(os.path.join(save_dir, "calibration.json"), "w") as fh:
-        json.dump(doc, fh, indent=1)
-    with open(os.path.join(save_dir, "calibration_bins.csv"), "w") as fh:
-        fh.write(",".join(("view",) + MT.CALIBRATION_BIN_COLUMNS) + "\n")
-        for name, v in doc["views"].items():
-            for r in v["table"]:
-                fh.write(",".join([name] + [_cell(r[c]) for c in MT.CALIBRATION_BIN_COLUMNS]) + "\n")
+    _write_json(save_dir, "calibration.json", doc)
+    _write_csv(save_dir, "calibration_bins.csv", ("view",) + MT.CALIBRATION_BIN_COLUMNS,
+               ([name] + [r[c] for c in MT.CALIBRATION_BIN_COLUMNS] for name, v in doc["views"].items() for r in v["table"]))
     return doc
 
 
@@ -329,19 +337,11 @@ def report_boundary(bands, rows, radii, tolerance, save_dir):
     print(f'    Hausdorff distance over {doc["patches"]} patches: mean {doc["mean_hausdorff"]:.6f} median '
           f'{doc["median_hausdorff"]:.6f} ({doc["infinite_hausdorff"]} infinite, {doc["zero_hausdorff"]} zero)')
     os.makedirs(save_dir, exist_ok=True)
-    with open(os.path.join(save_dir, "boundary_bands.json"), "w") as fh:
-        json.dump({"radii": list(radii), "bands": bands}, fh, indent=1)
-    with open(os.path.join(save_dir, "boundary_bands.csv"), "w") as fh:
-        fh.write(",".join(MT.BAND_COLUMNS) + "\n")
-        for r in bands:
-            fh.write(",".join(_cell(r[c]) for c in MT.BAND_COLUMNS) + "\n")
+    _write_json(save_dir, "boundary_bands.json", {"radii": list(radii), "bands": bands})
+    _write_csv(save_dir, "boundary_bands.csv", MT.BAND_COLUMNS, ([r[c] for c in MT.BAND_COLUMNS] for r in bands))
     cols = MT.boundary_report_columns(rows)
-    with open(os.path.join(save_dir, "patch_boundary.csv"), "w") as fh:
-        fh.write(",".join(cols) + "\n")
-        for r in rows:
-            fh.write(",".join(_cell(r[c]) for c in cols) + "\n")
-    with open(os.path.join(save_dir, "patch_boundary.json"), "w") as fh:
-        json.dump(doc, fh, indent=1)
+    _write_csv(save_dir, "patch_boundary.csv", cols, ([r[c] for c in cols] for r in rows))
+    _write_json(save_dir, "patch_boundary.json", doc)
     return dict(doc, bands=bands, rows=rows)
 
 
@@ -355,12 +355,8 @@ def report_patches(rows, save_dir):
           f'AUC mean {doc["mean_auc"]:.6f} median {doc["median_auc"]:.6f}')
     os.makedirs(save_dir, exist_ok=True)
     cols = MT.patch_report_columns(rows)
-    with open(os.path.join(save_dir, "patch_performance.csv"), "w") as fh:
-        fh.write(",".join(cols) + "\n")
-        for r in rows:
-            fh.write(",".join(repr(r[c]) if isinstance(r[c], float) else str(r[c]) for c in cols) + "\n")
-    with open(os.path.join(save_dir, "patch_performance.json"), "w") as fh:
-        json.dump(doc, fh, indent=1)
+    _write_csv(save_dir, "patch_performance.csv", cols, ([r[c] for c in cols] for r in rows))
+    _write_json(save_dir, "patch_performance.json", doc)
     return dict(doc, rows=rows)
 
 
@@ -391,13 +387,9 @@ def report_sweep(curve, target_coverage, save_dir):
             print(f'    target coverage {target_coverage}: s_cut_off {cut} (coverage {r["coverage"]:.6f}, '
                   f'risk {r["risk"]:.6f}, mIoU {r["mIoU"]:.6f})')
     os.makedirs(save_dir, exist_ok=True)
-    with open(os.path.join(save_dir, "risk_coverage.json"), "w") as fh:
-        json.dump(doc, fh, indent=1)
-    with open(os.path.join(save_dir, "risk_coverage.csv"), "w") as fh:
-        fh.write(",".join(CSV_COLUMNS + ("cm00", "cm01", "cm10", "cm11")) + "\n")
-        for r in curve:
-            cm = [int(v) for row in r["confusion_matrix"] for v in row]
-            fh.write(",".join([repr(r[c]) for c in CSV_COLUMNS] + [str(v) for v in cm]) + "\n")
+    _write_json(save_dir, "risk_coverage.json", doc)
+    _write_csv(save_dir, "risk_coverage.csv", CSV_COLUMNS + ("cm00", "cm01", "cm10", "cm11"),
+               ([r[c] for c in CSV_COLUMNS] + [int(v) for row in r["confusion_matrix"] for v in row] for r in curve))
     return doc
 
 

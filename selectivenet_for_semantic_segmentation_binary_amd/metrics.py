@@ -99,6 +99,31 @@ def _bisect(pred) -> float:
     return float(_ordered(hi))
 
 
+def _check_planes(who, selective, output, target, selection, per_patch=False, ids=None, noun=None):
+    """The argument rules the `add_batch` methods share; `who` names the class in the message."""
+    for name, t in (("output", output), ("target", target), ("selection", selection)):
+        if t is not None and (t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise RuntimeError(f"{who}.add_batch: {name} must be a contiguous cuda fp32 tensor")
+    if per_patch:
+        if output.dim() != 3:
+            raise ValueError(f"{who}.add_batch: output must be (N, H, W), got {tuple(output.shape)}")
+        if target.shape != output.shape or (selection is not None and selection.shape != output.shape):
+            raise ValueError(f"{who}.add_batch: output, target and selection must have the same shape")
+    elif output.numel() != target.numel() or (selection is not None and selection.numel() != output.numel()):
+        raise ValueError(f"{who}.add_batch: output, target and selection must have the same size")
+    if selective and selection is None:
+        raise ValueError(f"selective {noun or who} needs the selection logits")
+    if ids is not None and len(ids) != output.shape[0]:
+        raise ValueError(f"{who}.add_batch: {len(ids)} ids for {output.shape[0]} patches")
+
+
+def _host_sums(counts: torch.Tensor) -> np.ndarray:
+    """A device tensor of counts summed over the data-parallel ranks, on the host as int64 (one synchronisation)."""
+    c = counts.clone()
+    parallel.allreduce_sums(c)
+    return c.cpu().numpy().astype(np.int64)
+
+
 class SegMetrics:
     """Device-side Evaluator (utils/compute_metric.py:4-80) for num_class = 2.
 
@@ -117,21 +142,13 @@ class SegMetrics:
         self.counts.zero_()
 
     def add_batch(self, output: torch.Tensor, target: torch.Tensor, selection: torch.Tensor | None = None):
-        for name, t in (("output", output), ("target", target), ("selection", selection)):
-            if t is not None and (t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous()):
-                raise RuntimeError(f"SegMetrics.add_batch: {name} must be a contiguous cuda fp32 tensor")
-        if output.numel() != target.numel() or (selection is not None and selection.numel() != output.numel()):
-            raise ValueError("SegMetrics.add_batch: output, target and selection must have the same size")
-        if self.selective and selection is None:
-            raise ValueError("selective Evaluator needs the selection logits")
+        _check_planes("SegMetrics", self.selective, output, target, selection, noun="Evaluator")
         sel = selection if self.selective else None
         K.call("selunet_seg_metrics", K.ptr(output), K.ptr(sel), K.ptr(target), output.numel(), self.t_out,
                self.t_sel, K.ptr(self.counts), K.stream_ptr())
 
     def raw(self) -> np.ndarray:
-        c = self.counts.clone()
-        parallel.allreduce_sums(c)
-        return c.cpu().numpy().astype(np.int64)
+        return _host_sums(self.counts)
 
     def confusion_matrix(self) -> np.ndarray:
         return self.raw()[:4].reshape(2, 2).astype(np.float64)
@@ -204,18 +221,12 @@ class SelectiveSweep:
     def add_batch(self, output: torch.Tensor, target: torch.Tensor, selection: torch.Tensor):
         if selection is None:
             raise ValueError("SelectiveSweep.add_batch needs the selection logits")
-        for name, t in (("output", output), ("target", target), ("selection", selection)):
-            if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
-                raise RuntimeError(f"SelectiveSweep.add_batch: {name} must be a contiguous cuda fp32 tensor")
-        if output.numel() != target.numel() or selection.numel() != output.numel():
-            raise ValueError("SelectiveSweep.add_batch: output, target and selection must have the same size")
+        _check_planes("SelectiveSweep", True, output, target, selection)
         K.call("selunet_seg_metrics_sweep", K.ptr(output), K.ptr(selection), K.ptr(target), output.numel(),
                self.t_out, K.ptr(self.thresholds), len(self.s_cut_offs), K.ptr(self.bins), K.stream_ptr())
 
     def raw(self) -> np.ndarray:
-        c = self.bins.clone()
-        parallel.allreduce_sums(c)
-        return c.cpu().numpy().astype(np.int64)
+        return _host_sums(self.bins)
 
     def curve(self) -> list:
         return sweep_curve(self.raw(), self.s_cut_offs)
@@ -294,6 +305,45 @@ def patch_row(counts, auc, prefix="") -> dict:
     return {prefix + k: v for k, v in row.items()}
 
 
+class _PatchRows:
+    """The row store of a per-patch report: per batch one device tensor [passes][sections] of uint64 bits, a
+    section being [n][width] words of the batch's n patches, and the patches' ids. Nothing is copied until
+    `patches()`, which copies everything once."""
+
+    def __init__(self):
+        self._batches = []  # (n, device int64 tensor)
+        self._ids = []
+
+    def add(self, n, buf, ids):
+        self._batches.append((n, buf))
+        self._ids.extend([None] * n if ids is None else [str(i) for i in ids])
+
+    def patches(self, widths):
+        """(index, id, words) per patch in the order fed: words[pass][section] is the patch's row of that section
+        (sections of `widths` words per patch); the id defaults to patch_{index}."""
+        if not self._batches:
+            return
+        host = torch.cat([b.reshape(-1) for _, b in self._batches]).cpu().numpy()
+        at = index = 0
+        for n, buf in self._batches:
+            part = host[at:at + buf.numel()].reshape(buf.shape[0], -1)
+            at += buf.numel()
+            sections = [[s.reshape(n, -1) for s in np.split(p, np.cumsum(widths)[:-1] * n)] for p in part]
+            for i in range(n):
+                pid = self._ids[index] if self._ids[index] is not None else f"patch_{index}"
+                yield index, pid, [[s[i] for s in p] for p in sections]
+                index += 1
+
+
+def _finite_stats(values) -> tuple:
+    """(count, mean, median) of the finite values; the mean and the median are NaN when there is none."""
+    v = np.array(values, np.float64)
+    finite = v[np.isfinite(v)]
+    if not len(finite):
+        return 0, float("nan"), float("nan")
+    return len(finite), float(finite.mean()), float(np.median(finite))
+
+
 class PatchReport:
     """One row per patch in the pass eval already makes: per batch, `selunet_seg_metrics_rows` (the
     Evaluator's counts per image) and `selunet_patch_auc` (the exact integer Mann-Whitney statistic of
@@ -309,22 +359,11 @@ class PatchReport:
         self.reset()
 
     def reset(self):
-        self._batches = []  # (n, device int64 tensor [passes][n*6 + n*4] of uint64 bits)
-        self._ids = []
+        self._rows = _PatchRows()  # per batch [passes][n*6 + n*4]
 
     def add_batch(self, output: torch.Tensor, target: torch.Tensor, selection: torch.Tensor | None = None, ids=None):
-        for name, t in (("output", output), ("target", target), ("selection", selection)):
-            if t is not None and (t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous()):
-                raise RuntimeError(f"PatchReport.add_batch: {name} must be a contiguous cuda fp32 tensor")
-        if output.dim() != 3:
-            raise ValueError(f"PatchReport.add_batch: output must be (N, H, W), got {tuple(output.shape)}")
-        if target.shape != output.shape or (selection is not None and selection.shape != output.shape):
-            raise ValueError("PatchReport.add_batch: output, target and selection must have the same shape")
-        if self.selective and selection is None:
-            raise ValueError("selective PatchReport needs the selection logits")
+        _check_planes("PatchReport", self.selective, output, target, selection, per_patch=True, ids=ids)
         n, hw = output.shape[0], output.shape[1] * output.shape[2]
-        if ids is not None and len(ids) != n:
-            raise ValueError(f"PatchReport.add_batch: {len(ids)} ids for {n} patches")
         passes = [None, selection] if self.selective else [None]
         buf = torch.zeros(len(passes), n * 10, dtype=torch.int64, device=output.device)
         stream = K.stream_ptr()
@@ -333,30 +372,20 @@ class PatchReport:
                    self.t_sel, buf[k].data_ptr(), stream)
             K.call("selunet_patch_auc", K.ptr(output), K.ptr(sel), K.ptr(target), n, hw, self.t_sel,
                    buf[k].data_ptr() + n * 6 * 8, stream)
-        self._batches.append((n, buf))
-        self._ids.extend([None] * n if ids is None else [str(i) for i in ids])
+        self._rows.add(n, buf, ids)
 
     def rows(self) -> list:
-        if not self._batches:
-            return []
-        host = torch.cat([b.reshape(-1) for _, b in self._batches]).cpu().numpy()
-        passes = 2 if self.selective else 1
-        rows, at = [], 0
-        for n, _ in self._batches:
-            part = host[at:at + passes * n * 10].reshape(passes, n * 10)
-            at += passes * n * 10
-            for i in range(n):
-                index = len(rows)
-                counts, auc = part[0, :n * 6].reshape(n, 6)[i], part[0, n * 6:].reshape(n, 4)[i]
-                row = {"index": index, "id": self._ids[index] if self._ids[index] is not None else f"patch_{index}",
-                       "pixels": int(counts[5])}
-                row.update(patch_row(counts, auc))
-                if self.selective:
-                    counts, auc = part[1, :n * 6].reshape(n, 6)[i], part[1, n * 6:].reshape(n, 4)[i]
-                    row["selected"] = int(counts[4])
-                    row["coverage"] = row["selected"] / row["pixels"]
-                    row.update(patch_row(counts, auc, prefix="sel_"))
-                rows.append(row)
+        rows = []
+        for index, pid, words in self._rows.patches((6, 4)):
+            counts, auc = words[0]
+            row = {"index": index, "id": pid, "pixels": int(counts[5])}
+            row.update(patch_row(counts, auc))
+            if self.selective:
+                counts, auc = words[1]
+                row["selected"] = int(counts[4])
+                row["coverage"] = row["selected"] / row["pixels"]
+                row.update(patch_row(counts, auc, prefix="sel_"))
+            rows.append(row)
         return rows
 
 
@@ -373,11 +402,8 @@ def patch_report_summary(rows) -> dict:
     when there is none); with selection the same over the selected pixels' AUCs."""
     doc = {"patches": len(rows)}
     for prefix in ("", "sel_") if rows and "selected" in rows[0] else ("",):
-        auc = np.array([r[prefix + "auc_score"] for r in rows], np.float64)
-        finite = auc[np.isfinite(auc)]
-        doc[prefix + "nan_auc"] = int(len(auc) - len(finite))
-        doc[prefix + "mean_auc"] = float(finite.mean()) if len(finite) else float("nan")
-        doc[prefix + "median_auc"] = float(np.median(finite)) if len(finite) else float("nan")
+        finite, mean, median = _finite_stats([r[prefix + "auc_score"] for r in rows])
+        doc.update({prefix + "nan_auc": len(rows) - finite, prefix + "mean_auc": mean, prefix + "median_auc": median})
     return doc
 
 
@@ -514,22 +540,11 @@ class BoundaryReport:
 
     def reset(self):
         self.bins.zero_()
-        self._batches = []  # (n, device int64 tensor [passes][n*6 + n*6] of uint64 bits)
-        self._ids = []
+        self._rows = _PatchRows()  # per batch [passes][n*6 + n*6]
 
     def add_batch(self, output: torch.Tensor, target: torch.Tensor, selection: torch.Tensor | None = None, ids=None):
-        for name, t in (("output", output), ("target", target), ("selection", selection)):
-            if t is not None and (t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous()):
-                raise RuntimeError(f"BoundaryReport.add_batch: {name} must be a contiguous cuda fp32 tensor")
-        if output.dim() != 3:
-            raise ValueError(f"BoundaryReport.add_batch: output must be (N, H, W), got {tuple(output.shape)}")
-        if target.shape != output.shape or (selection is not None and selection.shape != output.shape):
-            raise ValueError("BoundaryReport.add_batch: output, target and selection must have the same shape")
-        if self.selective and selection is None:
-            raise ValueError("selective BoundaryReport needs the selection logits")
+        _check_planes("BoundaryReport", self.selective, output, target, selection, per_patch=True, ids=ids)
         n, hw = output.shape[0], output.shape[1] * output.shape[2]
-        if ids is not None and len(ids) != n:
-            raise ValueError(f"BoundaryReport.add_batch: {len(ids)} ids for {n} patches")
         if hw % 4 or hw > 1 << 20 or max(output.shape[1:]) > K.EDT_MAX_SIDE:  # before anything is counted
             raise ValueError(f"BoundaryReport.add_batch: patches of {tuple(output.shape[1:])}: H * W must be a "
                              f"multiple of 4 and at most 2^20, H and W at most {K.EDT_MAX_SIDE}")
@@ -549,35 +564,23 @@ class BoundaryReport:
                    n, hw, self.t_out, self.t_sel, self.tol_sq, buf[k].data_ptr(), stream)
             K.call("selunet_seg_metrics_rows", K.ptr(output), K.ptr(s), K.ptr(target), n, hw, self.t_out,
                    self.t_sel, buf[k].data_ptr() + n * 6 * 8, stream)
-        self._batches.append((n, buf))
-        self._ids.extend([None] * n if ids is None else [str(i) for i in ids])
+        self._rows.add(n, buf, ids)
 
     def raw_bands(self) -> np.ndarray:
-        c = self.bins.clone()
-        parallel.allreduce_sums(c)
-        return c.cpu().numpy().astype(np.int64)
+        return _host_sums(self.bins)
 
     def bands(self) -> list:
         return band_table(self.raw_bands(), self.radii)
 
     def rows(self) -> list:
-        if not self._batches:
-            return []
-        host = torch.cat([b.reshape(-1) for _, b in self._batches]).cpu().numpy()
-        passes = 2 if self.selective else 1
-        rows, at = [], 0
-        for n, _ in self._batches:
-            part = host[at:at + passes * n * 12].reshape(passes, 2, n, 6)
-            at += passes * n * 12
-            for i in range(n):
-                index = len(rows)
-                row = {"index": index, "id": self._ids[index] if self._ids[index] is not None else f"patch_{index}",
-                       "pixels": int(part[0, 1, i, 5])}
-                row.update(boundary_patch(part[0, 0, i], part[0, 1, i]))
-                if self.selective:
-                    row["selected"] = int(part[1, 1, i, 4])
-                    row.update(boundary_patch(part[1, 0, i], part[1, 1, i], prefix="sel_"))
-                rows.append(row)
+        rows = []
+        for index, pid, words in self._rows.patches((6, 6)):
+            row = {"index": index, "id": pid, "pixels": int(words[0][1][5])}
+            row.update(boundary_patch(*words[0]))
+            if self.selective:
+                row["selected"] = int(words[1][1][4])
+                row.update(boundary_patch(*words[1], prefix="sel_"))
+            rows.append(row)
         return rows
 
 
@@ -594,12 +597,10 @@ def boundary_report_summary(rows) -> dict:
     median of the finite ones (NaN when there is none); with selection the same over the selected pixels."""
     doc = {"patches": len(rows)}
     for prefix in ("", "sel_") if rows and "selected" in rows[0] else ("",):
-        hd = np.array([r[prefix + "hausdorff"] for r in rows], np.float64)
-        finite = hd[np.isfinite(hd)]
-        doc[prefix + "infinite_hausdorff"] = int(len(hd) - len(finite))
-        doc[prefix + "zero_hausdorff"] = int((hd == 0).sum())
-        doc[prefix + "mean_hausdorff"] = float(finite.mean()) if len(finite) else float("nan")
-        doc[prefix + "median_hausdorff"] = float(np.median(finite)) if len(finite) else float("nan")
+        hd = [r[prefix + "hausdorff"] for r in rows]
+        finite, mean, median = _finite_stats(hd)
+        doc.update({prefix + "infinite_hausdorff": len(hd) - finite, prefix + "zero_hausdorff": hd.count(0),
+                    prefix + "mean_hausdorff": mean, prefix + "median_hausdorff": median})
     return doc
 
 
@@ -795,13 +796,7 @@ class CalibrationReport:
         return 1.0 if view == "selection" else self.temperature
 
     def add_batch(self, output: torch.Tensor, target: torch.Tensor, selection: torch.Tensor | None = None):
-        for name, t in (("output", output), ("target", target), ("selection", selection)):
-            if t is not None and (t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous()):
-                raise RuntimeError(f"CalibrationReport.add_batch: {name} must be a contiguous cuda fp32 tensor")
-        if output.numel() != target.numel() or (selection is not None and selection.numel() != output.numel()):
-            raise ValueError("CalibrationReport.add_batch: output, target and selection must have the same size")
-        if self.selective and selection is None:
-            raise ValueError("selective CalibrationReport needs the selection logits")
+        _check_planes("CalibrationReport", self.selective, output, target, selection)
         stream = K.stream_ptr()
         for i, view in enumerate(self.views):
             if view == "selection":
@@ -815,9 +810,7 @@ class CalibrationReport:
                    base + self.k * 5 * 8, base + (self._words - 2) * 8, stream)
 
     def raw(self) -> dict:
-        c = self.counts.clone()
-        parallel.allreduce_sums(c)
-        host = c.cpu().numpy().astype(np.int64)
+        host = _host_sums(self.counts)
         at = self.k * 5
         return {view: {"bins": host[i, :at].reshape(self.k, 5), "fine": host[i, at:-2].reshape(-1, 2),
                        "misc": host[i, -2:]} for i, view in enumerate(self.views)}

@@ -168,6 +168,80 @@ def test_seg_metrics(selective):
 
 
 @pytest.mark.parametrize("selective", [True, False])
+def test_every_entry_point_applies_one_pixel_rule(selective):
+    """Two images of 36 x 36 = 1296 pixels (a multiple of 4, two passes of patch_auc's 1024 threads, six of one
+    256-thread workgroup at IO_GRID = 1). Image 0 opens with every combination of an edge value of `out` (the two
+    thresholds, their fp32 neighbours, +-0, +-inf, NaN, +-40), an edge value of `sel` and a label of 0, 1, 2, 3, 255;
+    the rest is metrics_case's. The six selunet_seg_metrics counts equal the rule restated here in numpy, and every
+    other entry point's totals of the same pixels equal them."""
+    n, h, w = 2, 36, 36
+    hw, p = h * w, n * h * w
+    out, sel, tgt = (a[:p].copy() for a in metrics_case(5, 300))
+    edge = out[:13].copy()  # edge_case's 13 values
+    assert np.isnan(edge).sum() == 1 and {float(T_OUT), float(T_SEL), np.inf, -np.inf} <= set(edge.tolist())
+    labels = np.array([0, 1, 2, 3, 255], F32)
+    combos = edge.size ** 2 * labels.size
+    assert combos <= hw
+    out[:combos] = np.repeat(edge, edge.size * labels.size)
+    sel[:combos] = np.tile(np.repeat(edge, labels.size), edge.size)
+    tgt[:combos] = np.tile(labels, edge.size ** 2)
+
+    # the rule: label = uint8(target); selected iff no selection plane or sel >= t_sel; pred = out >= t_out
+    lab = tgt.astype(np.uint8)
+    with np.errstate(invalid="ignore"):
+        selected = sel >= T_SEL if selective else np.ones(p, bool)
+        pred = out >= T_OUT
+    cm = [int((selected & (lab == l) & (pred == q)).sum()) for l in (0, 1) for q in (False, True)]
+    want = np.array(cm + [int(selected.sum()), p], np.int64)
+    nan_pos = int((selected & (lab == 1) & np.isnan(out)).sum())
+    assert min(cm) > 0 and nan_pos > 0 and want[4] - sum(cm) > 0 and (not selective or want[4] < p)
+
+    shape = lambda a: a.reshape(n, h, w)  # noqa: E731
+    o, s_all, t = dev(shape(out)), dev(shape(sel)), dev(shape(tgt))
+    s = s_all if selective else None
+    d2t, d2p = MT.boundary_distance_sq(t, 0.5), MT.boundary_distance_sq(o, float(T_OUT))
+    r2 = (K.c_int32 * 2)(4, 100)
+    thr = dev(np.array([T_SEL], F32))
+    edges = dev(np.array([T_OUT], F32))
+    args = (float(T_OUT), float(T_SEL))
+
+    def run():
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.int64, device=DEV)  # noqa: E731
+        r = {"counts": z(6), "rows": z(n, 6), "sweep": z(2, 5), "bands": z(4, 6), "brows": z(n, 6), "auc": z(n, 4),
+             "calib": z(2, 5), "misc": z(2)}
+        st = K.stream_ptr()
+        K.call("selunet_seg_metrics", K.ptr(o), K.ptr(s), K.ptr(t), p, *args, K.ptr(r["counts"]), st)
+        K.call("selunet_seg_metrics_rows", K.ptr(o), K.ptr(s), K.ptr(t), n, hw, *args, K.ptr(r["rows"]), st)
+        K.call("selunet_seg_metrics_sweep", K.ptr(o), K.ptr(s_all), K.ptr(t), p, float(T_OUT), K.ptr(thr), 1,
+               K.ptr(r["sweep"]), st)
+        K.call("selunet_boundary_bands", K.ptr(o), K.ptr(s), K.ptr(t), K.ptr(d2t), n, hw, *args, r2, 2,
+               K.ptr(r["bands"]), st)
+        K.call("selunet_boundary_rows", K.ptr(o), K.ptr(s), K.ptr(t), K.ptr(d2t), K.ptr(d2p), n, hw, *args, 4,
+               K.ptr(r["brows"]), st)
+        K.call("selunet_patch_auc", K.ptr(o), K.ptr(s), K.ptr(t), n, hw, float(T_SEL), K.ptr(r["auc"]), st)
+        K.call("selunet_calibration_bins", K.ptr(o), None, K.ptr(s), K.ptr(t), p, 0, *args, K.ptr(edges), 1, 1.0,
+               K.ptr(r["calib"]), None, K.ptr(r["misc"]), st)
+        return r
+
+    got = under_grids(run)
+    assert np.array_equal(got["counts"], want)
+    assert np.array_equal(got["rows"].sum(0), want)
+    assert np.array_equal(got["bands"].sum(0), want)
+    # the sweep has no "no selection plane": its bin 1 is what t_sel selects, both bins together are every pixel
+    sweep = got["sweep"][1] if selective else got["sweep"].sum(0)
+    assert np.array_equal(sweep, want[:5]) and got["sweep"][:, 4].sum() == p
+    assert (got["brows"][:, 4].sum(), got["brows"][:, 5].sum()) == (want[1], want[2])  # fp = cm01, fn = cm10
+    assert got["auc"][:, 1:].sum() == want[:4].sum()  # n_pos + n_neg + n_nan: the counted pixels
+    non_events, events = got["calib"][:, 0].sum(), got["calib"][:, 1].sum()
+    nan_scores, other_labels = got["misc"]
+    assert events + nan_pos == want[2] + want[3]
+    assert non_events + events + nan_scores == want[:4].sum()
+    assert want[4] == want[:4].sum() + other_labels
+    # one edge at t_out: bin 1 holds the pixels predicted 1 (a NaN score predicts 0 and is in no bin)
+    assert (got["calib"][1, 0], got["calib"][1, 1]) == (want[1], want[3])
+
+
+@pytest.mark.parametrize("selective", [True, False])
 def test_seg_metrics_rows(selective):
     """Three images of 9648 pixels: gx = 3 by the launcher's own rule, so IO_GRID = 1 wraps what it does not."""
     n = 3
