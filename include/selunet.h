@@ -681,6 +681,27 @@ int selunet_prep_batch(const uint8_t* img, const uint8_t* lab, const uint8_t* fl
  * hematoxylin stain recombined alone by skimage.color.combine_stains; x [n][3][h][w]). */
 int selunet_prep_batch_mode(const uint8_t* img, const uint8_t* lab, const uint8_t* flips, int32_t n,
                             int32_t h, int32_t w, int32_t mode, float* x, float* target, void* stream);
+/* selunet_prep_batch_mode with the training augmentation deciding which three bytes and
+ * which label byte of the uint8 batch enter the same per-pixel conversion. All arrays are DEVICE arrays.
+ * For output pixel (y, x) of image b:
+ *   glass: uint8 [n] or NULL; 0 = none, 1..4 = a quadrant of the OUTPUT (hh = h / 2, hw = w / 2; 1: y < hh,
+ *     x < hw; 2: y < hh, x >= hw; 3: y >= hh, x < hw; 4: y >= hh, x >= hw). A pixel of that quadrant gets
+ *     byte_c = table[u(key[b], (y w + x) 3 + c) >> 20] and label byte 0. table: uint8 [4096], the glass model
+ *     0.96 + 0.005 N(0,1) quantised to bytes; key: uint32 [n];
+ *     u(k, i) = mix(mix(k) + i * 0x9E3779B9) in uint32 arithmetic,
+ *     mix(v): v ^= v >> 16; v *= 0x7feb352d; v ^= v >> 15; v *= 0x846ca68b; v ^= v >> 16.
+ *   geom: uint8 [n] or NULL (0); every other pixel is the source pixel img[b][xs][ys] when geom[b] & 4, else
+ *     img[b][ys][xs], with ys = h-1-y when geom[b] & 2 and xs = w-1-x when geom[b] & 1 (the `flips` of
+ *     selunet_prep_batch when bit 2 is clear); its label byte comes from the same place.
+ *   transposed: nonzero iff some geom[b] has bit 2 set (the caller knows its own draws: the call reads no
+ *     device memory). Then h == w is required; when zero, bit 2 of geom is ignored.
+ *   lut: uint8 [n][3][256] or NULL; byte_c = lut[b][c][byte_c] for pixels that are not glass.
+ * x / target as selunet_prep_batch_mode. EINVAL for a mode outside 0..2, w % 4 != 0, outputs not 16-B
+ * aligned, transposed with h != w or without geom, glass without table or key. */
+int selunet_prep_batch_aug(const uint8_t* img, const uint8_t* lab, const uint8_t* geom,
+                           const uint8_t* glass, const uint32_t* key, const uint8_t* lut,
+                           const uint8_t* table, int32_t transposed, int32_t n, int32_t h, int32_t w,
+                           int32_t mode, float* x, float* target, void* stream);
 /* Per-batch metrics of train.py:211-238 / eval.py:218-246 accumulated on the device:
  * counts[6] (uint64, caller-zeroed, accumulated across calls) = {cm[0][0], cm[0][1], cm[1][0],
  * cm[1][1], selected, total} with cm[label][pred] = Evaluator.confusion_matrix

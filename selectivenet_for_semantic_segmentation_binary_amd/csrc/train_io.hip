@@ -5,6 +5,9 @@
 //    per-image `RandomFlip` of utils/data_utils.py:108-125) and the fp32 BCE target
 //    (`label/255.0` truncated to uint8, utils/data_utils.py:220-221, then `.type(FloatTensor)`,
 //    train.py:189-191). Replaces the host-side PIL decode + numpy transforms of the DataLoader.
+//  * selunet_prep_batch_aug: the same with the training augmentation in front of the per-pixel conversion —
+//    the eight orientations of the square, a glass quadrant (the reference's unused PartialNonTissue,
+//    utils/data_utils.py:127-157) and a per-image colour table.
 //  * selunet_seg_metrics: the per-batch host metrics of train.py:211-238 / eval.py:218-246 —
 //    prediction threshold, selection threshold, rejection count and the Evaluator's 2x2
 //    confusion matrix (utils/compute_metric.py:10-26) — as integer counts accumulated on the
@@ -18,6 +21,7 @@
 // All are byte/int work (no MFMA) in one pass over the data with 16-B coalesced loads; at an eval
 // batch the metrics kernels are bound by their launch and their closing atomics, not by HBM.
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 #include "metrics_common.h"
@@ -58,6 +62,89 @@ __global__ void prep_batch_kernel(const uint8_t* __restrict__ img, const uint8_t
       for (int c = 0; c < CIN; ++c) xv[c][j] = v[c];
       // (label/255.0).astype(uint8): truncation, so only 255 -> 1
       tv[j] = (float)(uint8_t)((double)lab[src_row + xs] / 255.0);
+    }
+    const int64_t plane = (int64_t)h * w;
+    const int64_t o = (int64_t)y * w + xq * 4;
+#pragma unroll
+    for (int c = 0; c < CIN; ++c)
+      *reinterpret_cast<f32x4*>(x + ((int64_t)b * CIN + c) * plane + o) = f32x4{xv[c][0], xv[c][1], xv[c][2], xv[c][3]};
+    *reinterpret_cast<f32x4*>(target + (int64_t)b * plane + o) = f32x4{tv[0], tv[1], tv[2], tv[3]};
+  }
+}
+
+// Counter-based noise of the glass model: 32 uniform bits from (key, counter) alone, in uint32 arithmetic
+// (the lowbias32 finaliser twice, the counter spread by the golden ratio in between). The counter is an output
+// position, so the noise depends neither on the batch nor on the grid.
+__device__ __forceinline__ unsigned aug_mix(unsigned v) {
+  v ^= v >> 16;
+  v *= 0x7feb352du;
+  v ^= v >> 15;
+  v *= 0x846ca68bu;
+  v ^= v >> 16;
+  return v;
+}
+__device__ __forceinline__ unsigned aug_hash(unsigned key, unsigned counter) {
+  return aug_mix(aug_mix(key) + counter * 0x9E3779B9u);
+}
+
+// prep_batch_kernel with the training augmentation in front of the per-pixel conversion: the
+// same thread shape and stores; per output pixel it chooses which three bytes and which label byte enter
+// prep_pixel. Glass (quadrant `glass[b]` of the OUTPUT, 1..4): bytes table[hash >> 20], label 0. Elsewhere the
+// source pixel of geom[b] (bit 2 transposes, bit 1 flips rows, bit 0 columns: predict_tta.hip's T_k; a
+// transposed image is square), its bytes through lut[b][c][.] when given. gmask = 7 when the caller declared
+// transposed images (h == w, checked by the launcher), else 3: an undeclared bit 2 is ignored, never an
+// out-of-range read. A transposed image reads four source rows per thread (plain byte reads: §7l).
+// EXTRA: glass or lut may be given. Without either (flips and transposes alone) the per-pixel branch is compiled
+// out, so that a thread's sixteen byte loads are in flight together as in prep_batch_kernel (with the branch the
+// flips-only call took 32.0 us against 28.2 us at 128 x 256 x 256, profiles/augment_prep.txt).
+template <int CIN, bool HRGB, bool EXTRA>
+__global__ void prep_batch_aug_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ lab,
+                                      const uint8_t* __restrict__ geom, const uint8_t* __restrict__ glass,
+                                      const uint32_t* __restrict__ key, const uint8_t* __restrict__ lut,
+                                      const uint8_t* __restrict__ table, int gmask, int n, int h, int w,
+                                      float* __restrict__ x, float* __restrict__ target) {
+  const int wq = w >> 2;
+  const int hh = h >> 1, hw = w >> 1;
+  const int64_t total = (int64_t)n * h * wq;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int xq = (int)(i % wq);
+    const int64_t r = i / wq;
+    const int y = (int)(r % h);
+    const int b = (int)(r / h);
+    const int f = geom ? geom[b] & gmask : 0;
+    const int gl = EXTRA && glass ? glass[b] : 0;
+    // quadrant gl - 1 = 2 * (lower half) + (right half)
+    const bool glass_row = gl >= 1 && gl <= 4 && ((y >= hh) == (((gl - 1) & 2) != 0));
+    const bool glass_right = ((gl - 1) & 1) != 0;
+    const unsigned k = glass_row ? key[b] : 0u;
+    const int ys = (f & 2) ? h - 1 - y : y;
+    const int64_t src_img = (int64_t)b * h * w;
+    const uint8_t* lt = EXTRA && lut ? lut + (int64_t)b * 768 : nullptr;
+    float xv[CIN][4];
+    float tv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int xo = xq * 4 + j;
+      unsigned p[3], l;
+      if (EXTRA && glass_row && ((xo >= hw) == glass_right)) {
+        const unsigned c0 = ((unsigned)y * (unsigned)w + (unsigned)xo) * 3u;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) p[c] = table[aug_hash(k, c0 + c) >> 20];
+        l = 0;
+      } else {
+        const int xs = (f & 1) ? w - 1 - xo : xo;
+        const int64_t s = src_img + ((f & 4) ? (int64_t)xs * w + ys : (int64_t)ys * w + xs);
+        const uint8_t* q = img + s * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) p[c] = EXTRA && lt ? lt[c * 256 + q[c]] : q[c];
+        l = lab[s];
+      }
+      float v[CIN];
+      prep_pixel<CIN, HRGB>(p[0], p[1], p[2], v);
+#pragma unroll
+      for (int c = 0; c < CIN; ++c) xv[c][j] = v[c];
+      // (label/255.0).astype(uint8): truncation, so only 255 -> 1
+      tv[j] = (float)(uint8_t)((double)l / 255.0);
     }
     const int64_t plane = (int64_t)h * w;
     const int64_t o = (int64_t)y * w + xq * 4;
@@ -394,6 +481,30 @@ int selunet_prep_batch(const uint8_t* img, const uint8_t* lab, const uint8_t* fl
   hipLaunchKernelGGL(cin == 3 ? prep_batch_kernel<3> : prep_batch_kernel<2>, dim3(grid), dim3(IO_TPB), 0,
                      as_stream(stream), img, lab, flips, n, h, w, x, target);
   return check_launch("prep_batch");
+}
+
+int selunet_prep_batch_aug(const uint8_t* img, const uint8_t* lab, const uint8_t* geom, const uint8_t* glass,
+                           const uint32_t* key, const uint8_t* lut, const uint8_t* table, int32_t transposed,
+                           int32_t n, int32_t h, int32_t w, int32_t mode, float* x, float* target, void* stream) {
+  SELUNET_REQUIRE(mode >= 0 && mode <= 2, "prep_batch_aug: mode 0 'RGB', 1 'GH', 2 'H_RGB' (got %d)", mode);
+  SELUNET_REQUIRE(img && lab && x && target && n > 0 && h > 0 && w > 0, "prep_batch_aug: bad arguments");
+  SELUNET_REQUIRE(w % 4 == 0, "prep_batch_aug: width must be a multiple of 4 (got %d)", w);
+  SELUNET_REQUIRE(aligned(15, x, target), "prep_batch_aug: outputs must be 16-B aligned");
+  SELUNET_REQUIRE(!transposed || (geom && h == w),
+                  "prep_batch_aug: a transposed image (geom bit 2) needs geom and h == w (got %d x %d)", h, w);
+  SELUNET_REQUIRE(!glass || (table && key), "prep_batch_aug: glass needs the glass table and the keys");
+  SELUNET_REQUIRE(aligned(3, key), "prep_batch_aug: key must be 4-B aligned");
+  const int64_t total = (int64_t)n * h * (w / 4);
+  const unsigned grid = (unsigned)io_grid(cdiv(total, IO_TPB), 8192);
+  auto pick = [&](auto extra) {
+    constexpr bool E = decltype(extra)::value;
+    return mode == 0 ? prep_batch_aug_kernel<3, false, E>
+                     : mode == 1 ? prep_batch_aug_kernel<2, false, E> : prep_batch_aug_kernel<3, true, E>;
+  };
+  auto kernel = glass || lut ? pick(std::true_type{}) : pick(std::false_type{});
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(IO_TPB), 0, as_stream(stream), img, lab, geom, glass, key, lut, table,
+                     transposed ? 7 : 3, n, h, w, x, target);
+  return check_launch("prep_batch_aug");
 }
 
 int selunet_seg_metrics(const float* out, const float* sel, const float* target, int64_t p, float t_out, float t_sel,

@@ -7,7 +7,9 @@ The reference decodes every JPEG/PNG patch with PIL inside `PatchDataset.__getit
 (an `.npy` cache next to the patches, memory-mapped afterwards), each global batch is gathered
 into pinned memory by a prefetch thread, copied to the GPU as uint8 (4x fewer bytes than fp32)
 and expanded there. Data-parallel ranks take their contiguous chunk of every global batch
-(DataParallel's scatter, parallel.chunk_bounds).
+(DataParallel's scatter, parallel.chunk_bounds). Training augmentation beyond the reference's flips
+(transposes, glass quadrants, colour tables; DESIGN.md §7l, off by default) is decided per image on the host
+and applied per pixel in that same expansion (`selunet_prep_batch_aug`).
 
 Split construction (`construct_train_valid` / `construct_test`) follows
 utils/data_utils.py:49-86, including the module-level `np.random.seed(42)` the reference's
@@ -18,6 +20,7 @@ from __future__ import annotations
 import concurrent.futures as cf
 import hashlib
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -210,6 +213,101 @@ def prep_batch(images_u8: torch.Tensor, labels_u8: torch.Tensor, flips: torch.Te
     return x, t
 
 
+# ----------------------------------------------------------------------------- training augmentation
+GLASS_MEAN, GLASS_STD = 0.96, 0.005  # PartialNonTissue's glass (utils/data_utils.py:127-157), as predict --tissue
+_GLASS_TABLE = None
+_GLASS_TABLE_DEV = {}
+
+
+def glass_table() -> np.ndarray:
+    """uint8 [4096]: the glass model 0.96 + 0.005 N(0,1) quantised to bytes, by quantile:
+    T[j] = floor(255 clip(0.96 + 0.005 Phi^-1((j + 0.5) / 4096), 0, 1) + 0.5). A uniform 12-bit index into it
+    draws a glass byte without a device-side logf/cosf."""
+    global _GLASS_TABLE
+    if _GLASS_TABLE is None:
+        from statistics import NormalDist
+
+        inv = NormalDist().inv_cdf
+        z = np.array([inv((j + 0.5) / 4096) for j in range(4096)], np.float64)
+        t = np.floor(255 * np.clip(GLASS_MEAN + GLASS_STD * z, 0, 1) + 0.5).astype(np.uint8)
+        t.setflags(write=False)
+        _GLASS_TABLE = t
+    return _GLASS_TABLE
+
+
+def _glass_table_on(device) -> torch.Tensor:
+    device = torch.device(device)
+    if device not in _GLASS_TABLE_DEV:
+        _GLASS_TABLE_DEV[device] = torch.from_numpy(glass_table().copy()).to(device)
+    return _GLASS_TABLE_DEV[device]
+
+
+def color_lut(gamma, beta) -> np.ndarray:
+    """uint8 [n,3,256] from float64 [n,3] gamma and beta: per image and channel a scale (gamma) and an offset
+    (beta) of the optical density -log(v / 255), back as a byte:
+    lut[v] = floor(255 min(1, exp(-beta) (v / 255)^gamma) + 0.5), lut[0] = 0. The identity at (1, 0)."""
+    gamma, beta = np.asarray(gamma, np.float64), np.asarray(beta, np.float64)
+    if gamma.ndim != 2 or gamma.shape[1] != 3 or beta.shape != gamma.shape:
+        raise ValueError(f"color_lut: gamma and beta must both be [n,3] (got {gamma.shape} and {beta.shape})")
+    if not (np.isfinite(gamma).all() and np.isfinite(beta).all() and (gamma > 0).all()):
+        raise ValueError("color_lut: gamma must be finite and > 0, beta finite")
+    v = np.arange(256, dtype=np.float64) / 255.0
+    lut = np.floor(255 * np.minimum(1.0, np.exp(-beta)[..., None] * v ** gamma[..., None]) + 0.5).astype(np.uint8)
+    lut[..., 0] = 0
+    return lut
+
+
+def prep_batch_aug(images_u8: torch.Tensor, labels_u8: torch.Tensor, geom: torch.Tensor | None,
+                   glass: torch.Tensor | None = None, keys: torch.Tensor | None = None,
+                   lut: torch.Tensor | None = None, input_type: str = "RGB", transposed: bool | None = None):
+    """`prep_batch` with the training augmentation in front of the per-pixel conversion, all
+    on the GPU in the same single pass. Per image: geom uint8 [N] (bit 2 transposes, bit 1 flips rows, bit 0
+    columns; `flips` when bit 2 is clear), glass uint8 [N] (0, or the quadrant 1..4 of the output painted with
+    the glass model and label 0), keys int32 [N] (the bits of the uint32 noise key of that paint), lut uint8
+    [N,3,256] (`color_lut`; glass bypasses it). transposed: whether any geom has bit 2 set, for the caller that
+    knows its draws (BatchLoader); None reads geom back to find out. Returns (x, target) as `prep_batch`."""
+    if input_type not in _CIN:
+        raise ValueError(f"input_type {input_type!r}: 'RGB', 'GH' or 'H_RGB' (utils/data_utils.py:223-226)")
+    for name, t, dt in (("images", images_u8, torch.uint8), ("labels", labels_u8, torch.uint8),
+                        ("geom", geom, torch.uint8), ("glass", glass, torch.uint8), ("keys", keys, torch.int32),
+                        ("lut", lut, torch.uint8)):
+        if t is not None and (t.device.type != "cuda" or t.dtype != dt or not t.is_contiguous()):
+            raise RuntimeError(f"prep_batch_aug: {name} must be a contiguous cuda {str(dt)[6:]} tensor")
+    n, h, w, c_img = images_u8.shape
+    if c_img != 3:
+        raise ValueError(f"prep_batch_aug: images must be RGB [N,H,W,3] uint8 (got {tuple(images_u8.shape)})")
+    if labels_u8.shape != (n, h, w):
+        raise ValueError("prep_batch_aug: labels must be [N,H,W]")
+    for name, t in (("geom", geom), ("glass", glass), ("keys", keys)):
+        if t is not None and t.shape != (n,):
+            raise ValueError(f"prep_batch_aug: {name} must be [N]")
+    if lut is not None and lut.shape != (n, 3, 256):
+        raise ValueError(f"prep_batch_aug: lut must be [N,3,256] (got {tuple(lut.shape)})")
+    if glass is not None and keys is None:
+        raise ValueError("prep_batch_aug: glass needs keys")
+    if transposed is None:
+        transposed = geom is not None and bool((geom & 4).any())
+    x = torch.empty(n, _CIN[input_type], h, w, dtype=torch.float32, device=images_u8.device)
+    t = torch.empty(n, h, w, dtype=torch.float32, device=images_u8.device)
+    table = None if glass is None else _glass_table_on(images_u8.device)
+    K.call("selunet_prep_batch_aug", K.ptr(images_u8), K.ptr(labels_u8), K.ptr(geom), K.ptr(glass), K.ptr(keys),
+           K.ptr(lut), K.ptr(table), int(bool(transposed)), n, h, w, _MODE[input_type], K.ptr(x), K.ptr(t),
+           K.stream_ptr())
+    return x, t
+
+
+AUG_STREAM = 0xA06D4  # second seed word of the augmentation generator: never the shuffle/flip stream
+
+
+class AugRows(NamedTuple):
+    """The augmentation of one rank's chunk of a global batch, per image (a plan item's fourth element)."""
+    geom: np.ndarray          # uint8: flip bits 0 and 1 as ever, bit 2 the transpose
+    glass: np.ndarray | None  # uint8 0..4 (aug_glass > 0)
+    key: np.ndarray | None    # uint32 noise keys (aug_glass > 0)
+    gamma: np.ndarray | None  # float64 [n,3] (aug_color > 0)
+    beta: np.ndarray | None
+
+
 class BatchLoader:
     """Global batches of a PatchSet, this rank's contiguous chunk of each, prepared on the GPU.
 
@@ -218,13 +316,31 @@ class BatchLoader:
     image, fliplr with p=0.5 then flipud with p=0.5 (RandomFlip, utils/data_utils.py:108-125).
     A final global batch too small to give every rank at least one image is dropped under data
     parallelism (DataParallel would run it on fewer replicas); `dropped` reports it.
+
+    Training augmentation beyond the reference's flips, all off by default and then not a call
+    different: aug_d4 also transposes with p=0.5 (with the two flips: the eight orientations of the square);
+    aug_glass = P paints, with probability P, one uniformly drawn quadrant with the glass model and label 0
+    (PartialNonTissue, utils/data_utils.py:127-157; 0.25 is its randint(1,5) == 1); aug_color = sigma draws a
+    per-channel gamma ~ U(1-sigma, 1+sigma) and beta ~ U(-sigma, sigma) of `color_lut`. Shuffle and flips keep
+    their generator and draws; the augmentation has its own, PCG64([seed + epoch, AUG_STREAM]), from which every
+    draw is made per dataset index in one fixed order whichever options are on (`_aug_draws`), so an option
+    never moves another's draws and every rank computes the same plan.
     """
 
     def __init__(self, ds: PatchSet, batch_size: int, shuffle: bool, random_flip: bool, device, seed: int = 0,
-                 max_batches: int = 0, input_type: str = "RGB"):
+                 max_batches: int = 0, input_type: str = "RGB", aug_d4: bool = False, aug_glass: float = 0.0,
+                 aug_color: float = 0.0):
         self.ds, self.bs, self.shuffle, self.flip = ds, int(batch_size), shuffle, random_flip
         self.input_type = input_type
         self.device, self.seed, self.max_batches = device, seed, max_batches
+        if not 0.0 <= aug_glass <= 1.0:
+            raise ValueError(f"BatchLoader: aug_glass is a probability in [0, 1] (got {aug_glass})")
+        if not 0.0 <= aug_color <= 0.5:
+            raise ValueError(f"BatchLoader: aug_color must be in [0, 0.5] (got {aug_color})")
+        if aug_d4 and ds.hw[0] != ds.hw[1]:
+            raise ValueError(f"BatchLoader: aug_d4 transposes, which needs square patches (got {ds.hw})")
+        self.aug_d4, self.aug_glass, self.aug_color = bool(aug_d4), float(aug_glass), float(aug_color)
+        self.aug = self.aug_d4 or self.aug_glass > 0 or self.aug_color > 0
         self.epoch = 0
         self.dropped = 0
         self._pool = cf.ThreadPoolExecutor(max_workers=1)
@@ -232,6 +348,16 @@ class BatchLoader:
 
     def set_epoch(self, epoch: int):
         self.epoch = int(epoch)
+
+    def _aug_draws(self, n):
+        """Every augmentation draw of the epoch, per dataset index, in the fixed order: the transpose coin; the
+        glass uniform and the quadrant; the noise key; the colour uniforms [n, (gamma, beta), channel]."""
+        rng = np.random.Generator(np.random.PCG64([self.seed + self.epoch, AUG_STREAM]))
+        transpose = rng.random(n) > 0.5
+        glass_u, quadrant = rng.random(n), rng.integers(1, 5, n)
+        key = rng.integers(0, 2 ** 32, n, dtype=np.uint32)
+        color_u = rng.random((n, 2, 3))
+        return transpose, glass_u, quadrant, key, color_u
 
     def _plan(self):
         n = len(self.ds)
@@ -241,6 +367,12 @@ class BatchLoader:
         if self.flip:
             r = rng.random((n, 2))
             flips = ((r[:, 0] > 0.5) * 1 + (r[:, 1] > 0.5) * 2).astype(np.uint8)
+        if self.aug:
+            transpose, glass_u, quadrant, key, color_u = self._aug_draws(n)
+            geom = (flips | (transpose * self.aug_d4 * 4)).astype(np.uint8)
+            glass = np.where(glass_u < self.aug_glass, quadrant, 0).astype(np.uint8)
+            gamma = 1.0 + self.aug_color * (2.0 * color_u[:, 0] - 1.0)
+            beta = self.aug_color * (2.0 * color_u[:, 1] - 1.0)
         world, rank = parallel.world_size(), parallel.rank()
         batches = []
         for b0 in range(0, n, self.bs):
@@ -250,19 +382,35 @@ class BatchLoader:
                 self.dropped += 1
                 continue
             lo, hi = parallel.chunk_bounds(len(idx), rank, world)
-            batches.append((len(idx), idx[lo:hi], flips[order[b0:b0 + self.bs]][lo:hi]))
+            item = (len(idx), idx[lo:hi], flips[order[b0:b0 + self.bs]][lo:hi])
+            if self.aug:
+                rows, on_g, on_c = idx[lo:hi], self.aug_glass > 0, self.aug_color > 0
+                item += (AugRows(geom[rows], glass[rows] if on_g else None, key[rows] if on_g else None,
+                                 gamma[rows] if on_c else None, beta[rows] if on_c else None),)
+            batches.append(item)
         if self.max_batches:
             batches = batches[:self.max_batches]
         return batches
 
     def _host(self, item):
-        gb, idx, fl = item
+        """(global batch size, pinned host tensors, transposed): images, labels and the flips, or with an
+        augmentation (images, labels, geom, glass, keys, lut), absent ones None; transposed: some geom has bit 2."""
+        gb, idx, fl = item[:3]
         srt = np.argsort(idx, kind="stable")  # sorted reads from a memory map, then restore the order
         inv = np.empty_like(srt)
         inv[srt] = np.arange(len(srt))
         im = torch.from_numpy(np.ascontiguousarray(self.ds.images[idx[srt]][inv])).pin_memory()
         lb = torch.from_numpy(np.ascontiguousarray(self.ds.labels[idx[srt]][inv])).pin_memory()
-        return gb, im, lb, torch.from_numpy(np.ascontiguousarray(fl)).pin_memory()
+
+        def pinned(a):
+            return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).pin_memory()
+
+        if not self.aug:
+            return gb, (im, lb, pinned(fl)), False
+        a = item[3]
+        lut = None if a.gamma is None else color_lut(a.gamma, a.beta)
+        key = None if a.key is None else a.key.view(np.int32)  # the bits, as a torch dtype
+        return gb, (im, lb, pinned(a.geom), pinned(a.glass), pinned(key), pinned(lut)), bool((a.geom & 4).any())
 
     def __len__(self):
         return len(self._plan())
@@ -270,14 +418,14 @@ class BatchLoader:
     def _upload(self, item, copy_stream):
         """Host batch -> device. On a GPU the copies run on `copy_stream` (an event marks their end), so
         batch i+1 crosses PCIe while step i computes instead of in front of step i+1."""
-        gb, im, lb, fl = item
+        gb, host, transposed = item
         if copy_stream is None:
-            return gb, im.to(self.device), lb.to(self.device), fl.to(self.device), None
+            return gb, [None if t is None else t.to(self.device) for t in host], transposed, None
         with torch.cuda.stream(copy_stream):
-            dev = [t.to(self.device, non_blocking=True) for t in (im, lb, fl)]
+            dev = [None if t is None else t.to(self.device, non_blocking=True) for t in host]
             ev = torch.cuda.Event()
             ev.record(copy_stream)
-        return (gb, *dev, ev)
+        return gb, dev, transposed, ev
 
     def __iter__(self):
         plan = self._plan()
@@ -293,14 +441,18 @@ class BatchLoader:
         for i in range(len(plan)):
             if i + 1 < len(plan):
                 fut = self._pool.submit(self._host, plan[i + 1])
-            gb, im, lb, fl, ev = pending
+            gb, dev, transposed, ev = pending
             if ev is not None:  # the step's stream waits for the copies; the allocator learns the new user
                 cur = torch.cuda.current_stream(self.device)
                 cur.wait_event(ev)
-                for t in (im, lb, fl):
-                    t.record_stream(cur)
+                for t in dev:
+                    if t is not None:
+                        t.record_stream(cur)
             parallel.set_global_batch(gb)
-            x, t = prep_batch(im, lb, fl, self.input_type)
+            if self.aug:
+                x, t = prep_batch_aug(*dev, input_type=self.input_type, transposed=transposed)
+            else:
+                x, t = prep_batch(*dev, self.input_type)
             yield x, t
             if i + 1 < len(plan):  # (the consumer has enqueued step i: this upload overlaps it)
                 pending = self._upload(fut.result(), cs)

@@ -27,6 +27,8 @@ What differs, by design:
     masks as train.py:207-219).
   * `--valid_fp32_path split` runs the per-epoch validation forwards (net.eval()) of an fp32 run on the
     training forward's split-fp16 kernels (`fp32_eval_path`); training steps are unaffected.
+  * `--aug_d4 1`, `--aug_glass P`, `--aug_color SIGMA` (all off by default) augment the training batches — never the
+    validation ones — inside the batch-preparation kernel: transposes, glass quadrants, colour tables.
   * TensorBoard scalars are written when torch.utils.tensorboard is importable, otherwise as JSON
     lines in `{log_dir}/{train,valid}/scalars.jsonl`.
 """
@@ -82,9 +84,22 @@ def parse_arguments(argv=None):
     parser.add_argument('--valid_fp32_path', type=str, default='exact', choices=['exact', 'split'],
                         help="conv kernels of the fp32 validation forwards: exact fp32, or the training forward's "
                              "split-fp16 kernels (the validation loop only)")
+    parser.add_argument('--aug_d4', type=int, default=0, choices=[0, 1],
+                        help='training patches also transposed with p = 0.5: with the two flips, the eight '
+                             'orientations of the square (what predict --tta d4 averages over)')
+    parser.add_argument('--aug_glass', type=float, default=0.0, metavar='P',
+                        help='probability that a training patch gets one quadrant painted as glass, label 0 '
+                             "(the reference's unused PartialNonTissue; 0.25 is its randint(1,5) == 1)")
+    parser.add_argument('--aug_color', type=float, default=0.0, metavar='SIGMA',
+                        help='per-channel colour jitter of the training patches in optical density: '
+                             'scale ~ U(1-SIGMA, 1+SIGMA), offset ~ U(-SIGMA, SIGMA); at most 0.5')
     args = parser.parse_args(argv)
     if args.valid_fp32_path == 'split' and args.compute_dtype == 'bf16':
         parser.error('--valid_fp32_path split is an fp32 path: not with --compute_dtype bf16')
+    if not 0.0 <= args.aug_glass <= 1.0:
+        parser.error(f'--aug_glass is a probability in [0, 1] (got {args.aug_glass})')
+    if not 0.0 <= args.aug_color <= 0.5:
+        parser.error(f'--aug_color must be in [0, 0.5] (got {args.aug_color})')
     return args
 
 
@@ -247,7 +262,8 @@ def train(args, ckpt_dir, log_dir):
 
     ds_train, ds_val = load_data(args, args.seed)
     loader_train = D.BatchLoader(ds_train, args.batch_size, shuffle=True, random_flip=True, device=device,
-                                 seed=args.seed, max_batches=args.steps_per_epoch, input_type=args.input_type)
+                                 seed=args.seed, max_batches=args.steps_per_epoch, input_type=args.input_type,
+                                 aug_d4=bool(args.aug_d4), aug_glass=args.aug_glass, aug_color=args.aug_color)
     loader_val = D.BatchLoader(ds_val, args.batch_size, shuffle=False, random_flip=False, device=device,
                                seed=args.seed, max_batches=args.val_steps, input_type=args.input_type)
     log(f'# of gpu: {world}, gpu id: {args.local_rank}\n')
