@@ -273,10 +273,12 @@ int selunet_conv3x3_wgrad_x2_bn_src(const selunet_gather* p, const selunet_gathe
 int selunet_conv3x3_x2(const selunet_gather* a, const float* w, int32_t n_cols, const selunet_epilogue* ep,
                        const float* amax0, const float* amax1, void* stream);
 const char* selunet_conv3x3_x2_kernel_name(const selunet_gather* a, int32_t n_cols, int32_t mode, int32_t split);
-/* Statistics slab rows (stats / colsum / BN-backward sums of the epilogue) selunet_conv3x3_x2 and
- * write for this operand: the layers SELUNET_OPT_X2D sends to the 64-column kernel
- * with two 256-thread workgroups per CU have min(16x16 tiles, 512) rows, others as
- * selunet_gemm_stats_rows. selunet_conv3x3_x2_kernel_name names the kernel a call would run. */
+/* Statistics slab rows (stats / colsum / BN-backward sums of the epilogue) selunet_conv3x3_x2
+ * writes for this operand: the layers SELUNET_OPT_X2D sends to the 64-column kernel
+ * with two 256-thread workgroups per CU have min(16x16 tiles, 512) rows; the 128-column layers
+ * under SELUNET_OPT_X2P min(16x16 tiles, 512 / column tiles); under SELUNET_OPT_TILE_QUEUE bit 0
+ * the others have one row per 16x16 tile, else as selunet_gemm_stats_rows.
+ * selunet_conv3x3_x2_kernel_name names the kernel a call would run. */
 int64_t selunet_conv3x3_x2_stats_rows(const selunet_gather* a, int32_t n_cols);
 /* Range word of a training-mode BatchNorm+ReLU output relu(gamma*xhat + beta) over `count` values
  * per channel: |xhat| <= sqrt(count - 1) for batch statistics (Samuelson's inequality), so
