@@ -992,6 +992,42 @@ int selunet_tile_tissue_counts(const uint8_t* plane, int64_t pitch, int32_t H, i
 int selunet_tissue_class_counts(const uint8_t* mask, int64_t mask_pitch, const uint8_t* plane, int64_t pitch,
                                 int32_t H, int32_t W, unsigned long long* counts, void* stream);
 
+/* ---- Macenko stain normalisation of whole-image prediction ----------------------
+ * Four per-pixel passes over img, uint8 [H][W][3] RGB on the device; the caller does the linear algebra
+ * between them. Integer arithmetic and integer atomics only: every result is the same bit for bit on every
+ * run. Common to all four:
+ *   od_q: DEVICE int32 [256], the optical density of a byte in Q12, round(4096 * -ln(max(v, 1) / 255));
+ *     every entry must lie in [0, 2^15) (the overflow bounds below rest on it).
+ *   A pixel is stained iff od_q of all three of its bytes is >= beta_q.
+ *   B, P_q, T_q: HOST int32 arrays, row-major, read before the launch.
+ *   Outputs of the first three are caller-zeroed and accumulated (+=), so several images can share them.
+ * Common EINVAL: a null pointer; H or W outside [1, 65535]; od_q or dirs not 4-B aligned; a uint64 output
+ * not 8-B aligned. */
+#define SELUNET_STAIN_ANGLE_BINS 1024
+#define SELUNET_STAIN_CONC_BINS 1024
+#define SELUNET_STAIN_EXP_MAX 8192
+/* out: uint64 [10] += {n, sum r, sum g, sum b, sum rr, sum rg, sum rb, sum gg, sum gb, sum bb} of the
+ * optical densities (r, g, b) of the stained pixels. A product is < 2^30 and H W < 2^32: no overflow. */
+int selunet_stain_moments(const uint8_t* img, int32_t H, int32_t W, const int32_t* od_q, int32_t beta_q,
+                          unsigned long long* out, void* stream);
+/* out: uint64 [SELUNET_STAIN_ANGLE_BINS + 1]. Per stained pixel x = B[0] . od and y = B[1] . od (B: int32
+ * [2][3], two unit vectors in Q14); x <= 0 adds one to the last word ("skipped"), otherwise one to the bin
+ * #{k in 1 .. K-1 : dirs[k-1][0] y - dirs[k-1][1] x >= 0}. dirs: DEVICE int32 [K-1][2] = round(2^14 (cos,
+ * sin)) of theta_k = -pi/2 + k pi / K, which makes the predicate monotone in k (the kernel searches by
+ * halving and relies on it); entries in [-2^14, 2^14]. Also EINVAL: a row of B whose sum of |B| reaches 2^16
+ * (x and y are kept in 32 bits). */
+int selunet_stain_angle_hist(const uint8_t* img, int32_t H, int32_t W, const int32_t* od_q, int32_t beta_q,
+                             const int32_t* B, const int32_t* dirs, unsigned long long* out, void* stream);
+/* out: uint64 [2][SELUNET_STAIN_CONC_BINS]. Per stained pixel and stain s, c = P_q[s] . od (P_q: int32
+ * [2][3] in Q12, so c is Q24) adds one to bin clamp(c >> 17, 0, bins - 1) of row s: bins of 1/128. */
+int selunet_stain_conc_hist(const uint8_t* img, int32_t H, int32_t W, const int32_t* od_q, int32_t beta_q,
+                            const int32_t* P_q, unsigned long long* out, void* stream);
+/* out: uint8 [H][W][3]. Every pixel, stained or not: out_c = exp_q[clamp((T_q[c] . od + 2^15) >> 16, 0,
+ * n_exp - 1)] (T_q: int32 [3][3] in Q14; exp_q: DEVICE uint8 [n_exp], round(255 exp(-i / 1024))). Also
+ * EINVAL: n_exp outside [1, SELUNET_STAIN_EXP_MAX]; an entry of T_q with |T_q| >= 2^20; out overlapping img. */
+int selunet_stain_apply(const uint8_t* img, int32_t H, int32_t W, const int32_t* od_q, const int32_t* T_q,
+                        const uint8_t* exp_q, int32_t n_exp, uint8_t* out, void* stream);
+
 /* ---- multi-GPU overlap probe (bench/tools only, not on the training path) ------
  * Stand-in for one bucketed RCCL all-reduce kernel on a single GPU: n_wg workgroups of 256 threads
  * reduce-copy dst[i] += src[i] over their slices of [0, n) (n % 4 == 0, 16-B aligned), repeatedly,

@@ -20,6 +20,8 @@ Drop-in replacements for the reference's hot path (yellofi/SelectiveNet_for_sema
   `clean_mask`                           small-region / hole clean-up, on the device (predict_image(regions=...))
 * `tissue_plane`                         the glass / tissue mask of an image; predict_image(tissue=True) does not
                                         forward tiles without tissue and counts tumor over tissue
+* `stain`, `StainFit`, `MACENKO_TARGET`  Macenko stain normalisation on the device: stain.fit / fit_many / normalize;
+                                        predict_image(stain=target) normalises the image before it is tiled
 * `parallel.init_data_parallel`        <- torch.nn.DataParallel (train.py:131-134)
 
 All compute runs in libselunet.so (HIP, gfx950); there is no CPU fallback.
@@ -31,6 +33,7 @@ from .optim import Adam  # noqa: F401
 from .predict import TilePlan, clean_mask, label_regions, predict_image, region_table, tissue_plane  # noqa: F401
 from .selective_loss import (BCEWithLogitsLoss, CrossEntropyLoss, calc_selective_risk_image,  # noqa: F401
                              calc_selective_risk_image_b)
-from . import parallel  # noqa: F401
+from .stain import MACENKO_TARGET, StainFit  # noqa: F401
+from . import parallel, stain  # noqa: F401
 
 __version__ = "0.1.0"

@@ -32,6 +32,9 @@ CALIB_FRAC_BITS = 30  # SELUNET_CALIB_FRAC_BITS
 CALIB_NLL_BITS = 20  # SELUNET_CALIB_NLL_BITS
 CALIB_NLL_MAX = 1024  # SELUNET_CALIB_NLL_MAX
 CALIB_FINE_CELLS = 4098  # SELUNET_CALIB_FINE_CELLS
+STAIN_ANGLE_BINS = 1024  # SELUNET_STAIN_ANGLE_BINS
+STAIN_CONC_BINS = 1024  # SELUNET_STAIN_CONC_BINS
+STAIN_EXP_MAX = 8192  # SELUNET_STAIN_EXP_MAX
 EDT_ROW_CHUNK = 256  # pixels of a row one sweep of the EDT row pass's workgroup takes (csrc/boundary.hip)
 
 
@@ -230,6 +233,10 @@ SIGNATURES = {
     "selunet_tissue_plane": (c_int32, [P, c_int32, c_int32, c_int32, c_int32, P, c_int32, P]),
     "selunet_tile_tissue_counts": (c_int32, [P, c_int64, c_int32, c_int32, P, c_int32, c_int32, c_int32, c_int32, P, P]),
     "selunet_tissue_class_counts": (c_int32, [P, c_int64, P, c_int64, c_int32, c_int32, P, P]),
+    "selunet_stain_moments": (c_int32, [P, c_int32, c_int32, P, c_int32, P, P]),
+    "selunet_stain_angle_hist": (c_int32, [P, c_int32, c_int32, P, c_int32, P, P, P, P]),
+    "selunet_stain_conc_hist": (c_int32, [P, c_int32, c_int32, P, c_int32, P, P, P]),
+    "selunet_stain_apply": (c_int32, [P, c_int32, c_int32, P, P, P, c_int32, P, P]),
     "selunet_set_option": (c_int64, [c_int32, c_int64]),
     "selunet_cu_hold": (c_int32, [P, P, c_int64, c_int32, c_float, P]),
 }

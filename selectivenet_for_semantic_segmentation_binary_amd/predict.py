@@ -37,6 +37,14 @@ and max - min <= S) and do not forward a tile whose input window holds fewer tha
 selected, with logit -inf and prob8 0. `<stem>_tissue.png` (L: 255 tissue, 0 glass) is written, the image's predict.json
 entry gains "tissue_pixels", "tissue_counts", "tumor_fraction_of_tissue", "tiles_forwarded" and "tiles_total", and the
 document's head the rule's three numbers. Without `--tissue 1` nothing of that runs and every file is as before.
+
+`--stain_norm macenko`, `--stain_target FILE.json`, `--stain_beta B` (`predict_image(..., stain=, stain_beta=)`; DESIGN.md
+§7m) bring the image to the stain vectors and strengths of a target before it is tiled: a Macenko fit and re-rendering on
+the device, once per image (stain.py). The target is the published default or, better, the checkpoint's own training stain
+made by `python -m selectivenet_for_semantic_segmentation_binary_amd.stain fit`. The tissue plane of `--tissue` is still that
+of the original image. `<stem>_stain.png` is the normalised image, the image's predict.json entry gains "stain" (applied,
+reason, the fitted HE and maxC, n_stained, skipped, T) and the document's head the method, the target and beta. Where nothing
+can be fitted the image is predicted as it is and "applied" is false. Without the flag nothing of that runs.
 """
 from __future__ import annotations
 
@@ -51,6 +59,7 @@ import torch
 
 from . import _lib as K
 from . import metrics as MT
+from . import stain as ST
 from .data import _CIN, _MODE
 
 HALO_MIN = 56   # the receptive field reaches 51 pixels to either side; the next multiple of 8
@@ -577,6 +586,10 @@ class Prediction:
     tiles_kept: list | None = None
     tiles_forwarded: int | None = None
     tiles_total: int | None = None
+    # with stain=, else None: stain.normalize's info and the image that was predicted (uint8 [H,W,3] on
+    # the device; the input itself where nothing could be fitted)
+    stain: dict | None = None
+    stain_image: torch.Tensor | None = None
 
     @property
     def unanimous_fraction(self) -> float | None:
@@ -642,7 +655,8 @@ def predict_image(net, image_u8, *, tile: int = 512, halo: int = HALO_MIN, batch
                   input_type: str = "RGB", prob8: bool = True, allow_small_halo: bool = False,
                   tta: str = "none", regions: bool = False, min_region: int = 0, fill_holes: int = 0,
                   connectivity: int = 8, tissue: bool = False, tissue_bright: int = TISSUE_BRIGHT,
-                  tissue_spread: int = TISSUE_SPREAD, tissue_min_pixels: int = 1) -> Prediction:
+                  tissue_spread: int = TISSUE_SPREAD, tissue_min_pixels: int = 1, stain: ST.StainFit | None = None,
+                  stain_beta: float = ST.BETA, _tissue_image: torch.Tensor | None = None) -> Prediction:
     """Apply `net` (a UNet_B on a cuda device, in eval mode) to `image_u8`, a numpy or torch uint8 [H,W,3] RGB
     image of any size: gather -> net -> stitch per batch of `batch_size` tiles, on the current stream.
     tta: "none", or "flips" / "d4": the mean over the 4 flips / the 8 flips and transposes of the image
@@ -654,7 +668,31 @@ def predict_image(net, image_u8, *, tile: int = 512, halo: int = HALO_MIN, batch
     min(r,g,b) >= tissue_bright and max - min <= tissue_spread, and a tile whose input window holds fewer than
     tissue_min_pixels tissue pixels is not forwarded: its core is background, selected, logit -inf (selection
     +inf), prob8 0. The result gains tissue, tissue_counts, tiles_kept, tiles_forwarded and tiles_total; with the
-    default nothing of that runs."""
+    default nothing of that runs.
+    stain / stain_beta: with a `StainFit` target the image is normalised to it on the device
+    (`stain.normalize`) before it is tiled; gather, augmentation, stitch and regions run on the normalised image, the
+    tissue plane is still the original's, and the result gains stain and stain_image. With None nothing of that runs."""
+    if stain is not None:
+        if not isinstance(stain, ST.StainFit):
+            raise TypeError(f"predict_image: stain must be a stain.StainFit target or None (got {type(stain).__name__})")
+        ST.beta_q_of(stain_beta)
+        device = next(net.parameters()).device
+        if device.type != "cuda":
+            raise RuntimeError("predict_image runs on the GPU only (no CPU fallback); move the network to a cuda device")
+        img = image_u8 if torch.is_tensor(image_u8) else torch.from_numpy(np.ascontiguousarray(image_u8))
+        if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+            raise ValueError(f"predict_image: the image must be uint8 [H,W,3] RGB (got {img.dtype} {tuple(img.shape)})")
+        with torch.cuda.device(device):
+            img = img.to(device).contiguous()  # the one upload
+            normalised, info = ST.normalize(img, stain, stain_beta)
+        pred = predict_image(net, normalised, tile=tile, halo=halo, batch_size=batch_size, cut_off=cut_off,
+                             s_cut_off=s_cut_off, single_scale=single_scale, input_type=input_type, prob8=prob8,
+                             allow_small_halo=allow_small_halo, tta=tta, regions=regions, min_region=min_region,
+                             fill_holes=fill_holes, connectivity=connectivity, tissue=tissue, tissue_bright=tissue_bright,
+                             tissue_spread=tissue_spread, tissue_min_pixels=tissue_min_pixels,
+                             _tissue_image=img if tissue else None)
+        pred.stain, pred.stain_image = info, normalised
+        return pred
     if tta not in TTA_MEMBERS:
         raise ValueError(f"predict_image: tta {tta!r}: one of {', '.join(map(repr, TTA_MEMBERS))}")
     _tissue_args("predict_image", tissue_bright, tissue_spread, tissue_min_pixels)
@@ -685,7 +723,7 @@ def predict_image(net, image_u8, *, tile: int = 512, halo: int = HALO_MIN, batch
         pred = predict_image(net, img, tile=tile, halo=halo, batch_size=batch_size, cut_off=cut_off,
                              s_cut_off=s_cut_off, single_scale=single_scale, input_type=input_type, prob8=prob8,
                              allow_small_halo=allow_small_halo, tta=tta, tissue=tissue, tissue_bright=tissue_bright,
-                             tissue_spread=tissue_spread, tissue_min_pixels=tissue_min_pixels)
+                             tissue_spread=tissue_spread, tissue_min_pixels=tissue_min_pixels, _tissue_image=_tissue_image)
         with torch.cuda.device(device):  # the stages read the mask and prob8 only: any forward path, any tta
             pred.regions, pred.counts, *done = clean_mask(pred.mask, pred.prob8, int(min_region), int(fill_holes),
                                                           connectivity)
@@ -695,13 +733,14 @@ def predict_image(net, image_u8, *, tile: int = 512, halo: int = HALO_MIN, batch
         return pred
     if tta != "none":
         return _predict_tta(net, img, device, plan, TTA_MEMBERS[tta], batch_size, t_out, t_sel, input_type, prob8,
-                            allow_small_halo, rule)
+                            allow_small_halo, rule, _tissue_image)
     with torch.cuda.device(device), torch.no_grad():
         img = img.to(device).contiguous()  # the one upload
         origins = torch.from_numpy(plan.origins).to(device)
         keep = glass = None
         if rule:
-            glass = tissue_plane(img, rule[0], rule[1])
+            # of the original where the image was stain-normalised: the same tiles are forwarded
+            glass = tissue_plane(img if _tissue_image is None else _tissue_image, rule[0], rule[1])
             # the one read before the first forward
             keep = tile_tissue_counts(glass, origins, tile, tile).cpu().numpy() >= rule[2]
         # the cores cover the canvases exactly once: no initial value is read
@@ -736,7 +775,7 @@ def predict_image(net, image_u8, *, tile: int = 512, halo: int = HALO_MIN, batch
 
 
 def _predict_tta(net, img, device, plan, members, batch_size, t_out, t_sel, input_type, prob8, allow_small_halo,
-                 rule=None):
+                 rule=None, tissue_image=None):
     """predict_image with test-time augmentation. Member k = 4 c + f is the prediction of the
     image of orientation class c (0: the image; 1: its transpose, formed once on the device) flipped by f
     (bit 1 rows, bit 0 columns), mapped back. Per class, members run one after another: flipped gather -> net
@@ -744,7 +783,8 @@ def _predict_tta(net, img, device, plan, members, batch_size, t_out, t_sel, inpu
     multiple of 8 pixels (zeros, never written); one finalize forms the mean and everything derived from it.
     rule = (bright, spread, min_pixels): every member skips the tiles of its own tiling whose
     window holds fewer than min_pixels tissue pixels; the window counts of all members are read at once before
-    the first forward, and a skipped core is accumulated as -inf (selection +inf)."""
+    the first forward, and a skipped core is accumulated as -inf (selection +inf). tissue_image: the
+    image the tissue planes are made of where `img` is its stain-normalised copy."""
     H, W, tile, halo = plan.H, plan.W, plan.tile, plan.halo
     selective = bool(net.selective)
     with torch.cuda.device(device), torch.no_grad():
@@ -762,7 +802,11 @@ def _predict_tta(net, img, device, plan, members, batch_size, t_out, t_sel, inpu
 
         kept = glass = None
         if rule:
-            glass = [tissue_plane(orientation(c)[0], rule[0], rule[1]) for c in range(members // 4)]  # per pixel
+            if tissue_image is None:
+                glass = [tissue_plane(orientation(c)[0], rule[0], rule[1]) for c in range(members // 4)]  # per pixel
+            else:
+                glass = [tissue_plane(image_transpose(tissue_image) if c else tissue_image, rule[0], rule[1])
+                         for c in range(members // 4)]
             sizes = [orientation(k // 4)[1].n for k in range(members)]
             window = torch.empty(sum(sizes), dtype=torch.int32, device=device)
             for k, part in enumerate(torch.split(window, sizes)):
@@ -847,7 +891,19 @@ def parse_arguments(argv=None):
     parser.add_argument('--tissue_spread', type=int, default=TISSUE_SPREAD, help='see --tissue_bright')
     parser.add_argument('--tissue_min_pixels', type=int, default=1,
                         help='a tile is forwarded iff its input window holds at least this many tissue pixels')
+    # ---- stain normalisation of the image before it is tiled
+    parser.add_argument('--stain_norm', type=str, default='none', choices=['none', 'macenko'],
+                        help='macenko: fit the image and re-render it with the stains of --stain_target, write <stem>_stain.png')
+    parser.add_argument('--stain_target', type=str, default=None,
+                        help='the target, a JSON file made by `python -m ...stain fit` from training images '
+                             '(default: the published Macenko reference)')
+    parser.add_argument('--stain_beta', type=float, default=ST.BETA,
+                        help='a pixel is fitted to iff each of its optical densities is at least this')
     args = parser.parse_args(argv)
+    if args.stain_target is not None and args.stain_norm == 'none':
+        parser.error('--stain_target needs --stain_norm macenko')
+    if not 0.0 < args.stain_beta < 5.5:
+        parser.error('--stain_beta must be in (0, 5.5), an optical density')
     if args.fp32_path == 'split' and args.compute_dtype == 'bf16':
         parser.error('--fp32_path split is an fp32 path: not with --compute_dtype bf16')
     if args.min_region < 0 or args.fill_holes < 0:
@@ -908,6 +964,8 @@ def image_record(path, pred: Prediction) -> dict:
         rec["tissue_counts"] = dict(zip(COUNT_NAMES, tc))
         rec["tumor_fraction_of_tissue"] = tc[1] / (tc[0] + tc[1]) if tc[0] + tc[1] else None
         rec["tiles_forwarded"], rec["tiles_total"] = int(pred.tiles_forwarded), int(pred.tiles_total)
+    if pred.stain is not None:  # only with stain normalisation
+        rec["stain"] = dict(pred.stain)
     return rec
 
 
@@ -942,6 +1000,9 @@ def predict_files(args) -> dict:
     files = list_inputs(args.input)
     ckpt = find_checkpoint(args.model_dir)
     TilePlan(8, 8, args.tile, args.halo)  # the tiling arguments, before anything is loaded
+    target = None
+    if args.stain_norm == 'macenko':
+        target = ST.MACENKO_TARGET if args.stain_target is None else ST.load_target(args.stain_target)
     device = torch.device("cuda", args.local_rank[0])
     torch.cuda.set_device(device)
     dt = torch.bfloat16 if args.compute_dtype == 'bf16' else torch.float32
@@ -956,6 +1017,9 @@ def predict_files(args) -> dict:
         doc.update(tissue_bright=args.tissue_bright, tissue_spread=args.tissue_spread,
                    tissue_min_pixels=args.tissue_min_pixels)
         doc["images"] = doc.pop("images")  # the list stays last
+    if target is not None:  # only with stain normalisation
+        doc.update(stain_norm=args.stain_norm, stain_target=target.to_json(), stain_beta=args.stain_beta)
+        doc["images"] = doc.pop("images")
     for path in files:
         image = np.array(Image.open(path).convert("RGB"))
         pred = predict_image(net, image, tile=args.tile, halo=args.halo, batch_size=args.batch_size,
@@ -963,7 +1027,8 @@ def predict_files(args) -> dict:
                              input_type=args.input_type, tta=args.tta, regions=bool(args.regions),
                              min_region=args.min_region, fill_holes=args.fill_holes, connectivity=args.connectivity,
                              tissue=bool(args.tissue), tissue_bright=args.tissue_bright,
-                             tissue_spread=args.tissue_spread, tissue_min_pixels=args.tissue_min_pixels)
+                             tissue_spread=args.tissue_spread, tissue_min_pixels=args.tissue_min_pixels, stain=target,
+                             stain_beta=args.stain_beta)
         stem = os.path.join(args.save_dir, os.path.splitext(os.path.basename(path))[0])
         mask = pred.mask.cpu().numpy()
         Image.fromarray(mask).save(stem + "_mask.png")
@@ -977,6 +1042,8 @@ def predict_files(args) -> dict:
             write_regions_csv(stem + "_regions.csv", pred.regions)
         if pred.tissue is not None:
             Image.fromarray(pred.tissue.cpu().numpy()).save(stem + "_tissue.png")
+        if pred.stain_image is not None:
+            Image.fromarray(pred.stain_image.cpu().numpy()).save(stem + "_stain.png")
         rec = image_record(path, pred)
         doc["images"].append(rec)
         c = rec["counts"]
